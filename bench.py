@@ -2,8 +2,15 @@
 """Benchmark of the multi-start travel-time sweep (the hot path of
 serial_new/sweep-tt-multistart.c) on MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+unit, ms_per_step = milliseconds per timed step, ...).  Everything else the benchmark measures
+runs only with --full: the rocprofv3 traffic passes, the plain-C host program leg, the CPU
+baselines, the instrumented solve behind `roofline` / `roofline_hbm` and, for the default
+workload, the HBM-regime run.  --dump-outputs DIR writes what the last timed step computed
+(a fixed, seeded sample of the converged boxes, see dump_outputs) as DIR/*.npy.
 
 Default workload (BASELINE.json metric config): synthetic 241x241x51 velocity volume (the
 real model is absent from the reference tree), the reference's default 818-offset star
@@ -198,7 +205,7 @@ def measure_traffic(args, kernel_patterns):
         d = tempfile.mkdtemp(prefix="ttsweep_pmc_", dir="/tmp")
         try:
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "--",
-                   sys.executable, os.path.abspath(__file__), "--child", "--steps", "1", "--warmup", "1",
+                   sys.executable, os.path.abspath(__file__), "--child", "--full", "--steps", "1", "--warmup", "1",
                    "--no-cpu"] + workload_args(args)
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=150, env=env, cwd="/tmp")
             if r.returncode != 0:
@@ -274,6 +281,29 @@ def host_program_end_to_end(P, shape, star, starts, v_host):
         return None
     finally:
         shutil.rmtree(d, ignore_errors=True)
+
+
+DUMP_BYTES = 56 << 20               # --dump-outputs: bytes written in all (values and their indices), under 64 MB
+DUMP_SEED = 20160507
+
+
+def dump_outputs(out_dir, boxes, nstart, cells):
+    """What the timed path returned in its last step: the converged travel-time boxes
+    [nstart, nx, ny, nz].  The same cells of every box - a fixed, seeded sample when the whole
+    set and its index exceed DUMP_BYTES, every cell otherwise - go to travel_times.npy (float32,
+    [nstart, cells sampled]); travel_times_index.npy (float64) holds their flat C-order
+    indices into one box.  Same arguments, same cells: two builds compare file for file."""
+    import torch
+    k = min(cells, DUMP_BYTES // (4 * nstart + 8))
+    if k == cells:
+        idx = np.arange(cells, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cells, size=k, replace=False, shuffle=False))
+    flat = boxes.reshape(nstart, cells)
+    tt = flat.index_select(1, torch.from_numpy(idx).to(flat.device)).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "travel_times.npy"), np.ascontiguousarray(tt, dtype=np.float32))
+    np.save(os.path.join(out_dir, "travel_times_index.npy"), idx.astype(np.float64))
 
 
 HBM_REGIME = {"grid": "1024,1024,512", "star": "six", "starts": "111", "nstarts": 14}
@@ -409,9 +439,14 @@ def main():
     ap.add_argument("--handoff", type=int, default=None, help="schedule knob: TTSWEEP_OPT_ASYNC_HANDOFF (workers publish successor units themselves)")
     ap.add_argument("--waves", type=int, default=None, choices=[-1, 4, 8], help="schedule knob: TTSWEEP_OPT_ASYNC_WAVES (waves that relax a unit)")
     ap.add_argument("--special", type=int, default=None, help="schedule knob: TTSWEEP_OPT_ASYNC_SPECIAL")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: rocprofv3 traffic passes, host-program leg, CPU "
+                         "baselines, the instrumented solve behind roofline / roofline_hbm, the HBM-regime run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (seeded sample of the boxes) as DIR/*.npy")
     ap.add_argument("--cpu-b2", action="store_true",
-                    help="BASELINE.md leg B2 in this run: start-1 relaxed to convergence in the reference's order on ONE host "
-                         "core with the CPU restatement (about 190 s; not part of the driver's default run)")
+                    help="with --full, BASELINE.md leg B2 in this run: start-1 relaxed to convergence in the reference's "
+                         "order on ONE host core with the CPU restatement (about 190 s; not part of --full by itself)")
     ap.add_argument("--defer-margin", type=float, default=None,
                     help="schedule knob: improvements are told at once only to units not nearer to the start by more than this (cells)")
     ap.add_argument("--prepass", type=int, default=0,
@@ -429,8 +464,14 @@ def main():
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                          "the multi-rank path on a box with fewer GPUs than ranks)")
     args = ap.parse_args()
-    if args.child:
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.cpu_b2 and not args.full:
+        ap.error("--cpu-b2 is a leg of --full")
+    if args.child or not args.full:
         args.no_cpu = args.no_traffic = args.no_host = True
+    if not args.full:
+        args.no_hbm_regime = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -604,7 +645,7 @@ def main():
     sweeps_local = 0            # passes launched (a pass relaxes only what is due)
     relaxed_local = 0           # cells actually relaxed against the whole star
     for _ in range(args.steps):
-        step(timed=True)
+        boxes = step(timed=True)
         st_ = sol.stats()
         sweeps_local += st_["sweeps_total"]
         relaxed_local += st_["cells_relaxed"]
@@ -634,39 +675,48 @@ def main():
     else:
         sweeps_all, relaxed_all = float(sweeps_local), float(relaxed_local)
 
-    # one extra, instrumented solve: HIP events around every sweep launch on the
-    # library's own stream (not part of the timed region)
-    sol.set_option(P.OPT_TIMING, 1)
-    sol.solve_device(my_starts, tt, init=True)
-    st = sol.stats()
-    sol.set_option(P.OPT_TIMING, 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, boxes, nstart, cells)
+    del boxes
+
+    st = st_
+    if args.full:
+        # one extra, instrumented solve: HIP events around every sweep launch on the
+        # library's own stream (not part of the timed region)
+        sol.set_option(P.OPT_TIMING, 1)
+        sol.solve_device(my_starts, tt, init=True)
+        st = sol.stats()
+        sol.set_option(P.OPT_TIMING, 0)
 
     failed = False
     if rank == 0:
-        kern_s = st["sweep_kernel_ms"] / 1e3
-        launches = max(st["launches"], 1)
-        alg_bytes = BYTES_PER_CELL_SWEEP * st["cells_relaxed"]
-        relax = st["relaxations_per_sweep"] * (st["cells_relaxed"] / cells)
-        flops = FLOPS_PER_RELAX * relax
-        gbs = alg_bytes / kern_s / 1e9 if kern_s > 0 else 0.0
-        tfl = flops / kern_s / 1e12 if kern_s > 0 else 0.0
-        kname = {1: "sweep_cell_kernel", 2: "plan_pass_kernel + sweep_units_kernel (one pass)" if st["launches"] > 1 else
-                 "sweep_units_kernel<16, np, true> (ONE launch per solve: ring planners + workers, convergence detected on the device)",
-                 3: ("column_solve_kernel (one launch per solve: column pipelines)" if st["launches"] == 1 else
-                     "tile_six_kernel / tile_sweep_kernel (one tile hyperplane of an ordering sweep)")}[st["kernel_variant"]]
-        common = {"kernel": kname, "launches": int(launches), "avg_launch_ms": st["sweep_kernel_ms"] / launches,
-                  "algorithmic_bytes_per_launch": alg_bytes / launches,
-                  "algorithmic_flops_per_launch": flops / launches,
-                  "traffic": traffic["bytes_per_launch"] if traffic else None,
-                  "traffic_source": traffic["source"] if traffic else
-                  "not measured in this run (--no-traffic, N > 1, or rocprofv3 unavailable)"}
-        hbm = dict({"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": gbs / HBM_PEAK_GBS}, **common)
-        valu = dict({"bound": "valu", "achieved": tfl, "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": tfl / VALU_PEAK_TFLOPS}, **common)
-        per_cell = f"{FLOPS_PER_RELAX * npull} flops per {BYTES_PER_CELL_SWEEP} B per cell*pass " \
-                   f"({npull} offsets; machine balance {BALANCE_FLOPS_PER_BYTE:.1f} flops/B)"
-        hbm["note"] = valu["note"] = per_cell + (": the vector ALUs bind" if valu_bound else ": HBM binds")
+        roofline = {}
+        if args.full:
+            kern_s = st["sweep_kernel_ms"] / 1e3
+            launches = max(st["launches"], 1)
+            alg_bytes = BYTES_PER_CELL_SWEEP * st["cells_relaxed"]
+            relax = st["relaxations_per_sweep"] * (st["cells_relaxed"] / cells)
+            flops = FLOPS_PER_RELAX * relax
+            gbs = alg_bytes / kern_s / 1e9 if kern_s > 0 else 0.0
+            tfl = flops / kern_s / 1e12 if kern_s > 0 else 0.0
+            kname = {1: "sweep_cell_kernel", 2: "plan_pass_kernel + sweep_units_kernel (one pass)" if st["launches"] > 1 else
+                     "sweep_units_kernel<16, np, true> (ONE launch per solve: ring planners + workers, convergence detected on the device)",
+                     3: ("column_solve_kernel (one launch per solve: column pipelines)" if st["launches"] == 1 else
+                         "tile_six_kernel / tile_sweep_kernel (one tile hyperplane of an ordering sweep)")}[st["kernel_variant"]]
+            common = {"kernel": kname, "launches": int(launches), "avg_launch_ms": st["sweep_kernel_ms"] / launches,
+                      "algorithmic_bytes_per_launch": alg_bytes / launches,
+                      "algorithmic_flops_per_launch": flops / launches,
+                      "traffic": traffic["bytes_per_launch"] if traffic else None,
+                      "traffic_source": traffic["source"] if traffic else
+                      "not measured in this run (--no-traffic, N > 1, or rocprofv3 unavailable)"}
+            hbm = dict({"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": gbs / HBM_PEAK_GBS}, **common)
+            valu = dict({"bound": "valu", "achieved": tfl, "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "frac": tfl / VALU_PEAK_TFLOPS}, **common)
+            per_cell = f"{FLOPS_PER_RELAX * npull} flops per {BYTES_PER_CELL_SWEEP} B per cell*pass " \
+                       f"({npull} offsets; machine balance {BALANCE_FLOPS_PER_BYTE:.1f} flops/B)"
+            hbm["note"] = valu["note"] = per_cell + (": the vector ALUs bind" if valu_bound else ": HBM binds")
+            roofline = {"roofline": valu if valu_bound else hbm, "roofline_hbm": hbm}
         gpu_s = dt / args.steps
         out = {
             "metric": f"Mcells*sweeps/s ({nx}x{ny}x{nz}, {len(offs)}-offset star, {nstart} starts, to convergence)",
@@ -685,7 +735,7 @@ def main():
                        "kernel_variant": st["kernel_variant"],
                        "driver": ("one launch per solve (ring planners + workers, convergence detected on the device)"
                                   if st["kernel_variant"] in (2, 3) and st["launches"] == 1 else "a launch (pair) per pass / hyperplane, convergence tested on the host"),
-                       "fallbacks": int(st.get("fallbacks", 0)) + (sum(r["fallbacks"] for r in ranks_info) if ranks_info else phase["fallbacks"]),
+                       "fallbacks": (int(st.get("fallbacks", 0)) if args.full else 0) + (sum(r["fallbacks"] for r in ranks_info) if ranks_info else phase["fallbacks"]),
                        "library": os.path.relpath(P._lib.LIB_PATH, ROOT),
                        "passes_per_start_mean": sweeps_all / args.steps / nstart,
                        "full_sweep_equivalents_per_start_mean": relaxed_all / cells / args.steps / nstart},
@@ -693,8 +743,7 @@ def main():
                           "schedule that converges with LESS relaxation scores LOWER here at the same speed per relaxation - "
                           "compare ms_per_step / time_to_solution across rounds and schedules (round 3: 34.3 ms at 4.79 "
                           "equivalents per start; this line's equivalents: config.full_sweep_equivalents_per_start_mean)",
-            "roofline": valu if valu_bound else hbm,
-            "roofline_hbm": hbm,
+            **roofline,
             "time_to_solution": {"gpu_all_starts_s": gpu_s, "gpu_per_start_s": gpu_s / nstart,
                                  "what": "seconds from initial boxes to converged boxes, all starts batched"},
         }

@@ -121,6 +121,40 @@ def vbox_fixture():
     print("vbox fixture", os.path.getsize(path), "bytes")
 
 
+def live_fixture():
+    """The reference's answers on the random inputs of tests/test_oracle.py::test_against_live_reference
+    and its reader / writer on the box of tests/test_headers.py::test_reference_reader_accepts_our_writer,
+    so that both tests run where the reference is absent."""
+    out, meta = {}, {}
+    rng = np.random.default_rng(7)
+    n = 0
+    for shape in ((13, 9, 8), (6, 17, 10)):
+        v = rng.uniform(0.1, 0.4, size=shape).astype(np.float32)
+        for n_off in (5, 40):
+            offs = rng.integers(-3, 4, size=(n_off, 3)).astype(np.int32)
+            offs = offs[np.any(offs != 0, axis=1)]
+            start = np.array([int(rng.integers(0, m)) for m in shape], np.int32)
+            (tt,), sweeps = O.ref_converge(v, offs, [start])
+            out.update({f"v_{n}": v, f"offs_{n}": offs, f"start_{n}": start, f"tt_{n}": tt})
+            meta[str(n)] = {"sweeps": int(sweeps)}
+            n += 1
+    # the reference writer's file for that box, and what the reference reader makes of it
+    v = synth(5, 4, 3, 9)
+    v[0, 0, 0] = -2.0
+    path = os.path.join(HERE, "_vbox_tmp.vbox")
+    assert O.ref().ttref_store_vbox(path.encode(), 2, 3, 4, 5, 4, 3, v.reshape(-1).copy())
+    hdr = np.zeros(6, np.int32)
+    got = np.zeros(v.size, np.float32)
+    assert O.ref().ttref_load_vbox(path.encode(), hdr, got, got.size) == 1
+    assert hdr.tolist() == [2, 3, 4, 5, 4, 3] and np.array_equal(got.reshape(v.shape), v)
+    out["vbox_values"] = v
+    out["vbox_bytes"] = np.frombuffer(open(path, "rb").read(), np.uint8)
+    os.remove(path)
+    out["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
+    np.savez_compressed(os.path.join(HERE, "live_ref.npz"), **out)
+    print("live_ref cases:", len(meta))
+
+
 def big_digests():
     """Converged 241x241x51 boxes of the reference: SHA-256 + spot values only."""
     v = synth(241, 241, 51, 20160507)
@@ -192,5 +226,6 @@ if __name__ == "__main__":
         sys.exit("reference not available: golden vectors can only be generated beside /root/reference")
     small_fixtures()
     vbox_fixture()
+    live_fixture()
     if args.big:
         big_digests()

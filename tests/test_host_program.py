@@ -146,11 +146,11 @@ def test_host_program_rejects_bad_input(exe, tmp_path):
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line(pkg, exe):
-    """bench.py (the driver's entry point): exactly one JSON line on stdout with the keys of
+    """bench.py --full (the driver's entry point): exactly one JSON line on stdout with the keys of
     the contract, the roofline and (with --no-cpu) no CPU leg; value = cells relaxed / time."""
     import json
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0",
                         "--nstarts", "2", "--no-cpu", "--no-traffic"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -175,3 +175,51 @@ def test_bench_prints_one_contract_line(pkg, exe):
     cells = 241 * 241 * 51
     eq = d["config"]["full_sweep_equivalents_per_start_mean"]
     assert abs(d["value"] - eq * 2 * cells / (d["ms_per_step"] / 1e3) / 1e6) < 1e-6 * d["value"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(pkg, tmp_path):
+    """bench.py without --full: the contract line of exactly --steps timed steps and none of the legs of --full;
+    --dump-outputs writes the sampled boxes of the last timed step, bit for bit the same cells of a solve here."""
+    import json
+    import sys
+    from conftest import assert_bit_equal
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+                        "--nstarts", "2", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "time_to_solution"):
+        assert key in d, key
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "Mcells*sweeps/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    for key in ("roofline", "roofline_hbm", "cpu_baseline", "cpu_baseline_all_cores", "end_to_end_host_program",
+                "roofline_hbm_regime"):
+        assert key not in d, key
+
+    assert sorted(os.listdir(out)) == ["travel_times.npy", "travel_times_index.npy"]
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 << 20
+    tt = np.load(out / "travel_times.npy")
+    idx = np.load(out / "travel_times_index.npy")
+    assert tt.dtype == np.float32 and idx.dtype == np.float64
+    shape = (241, 241, 51)
+    cells = shape[0] * shape[1] * shape[2]
+    assert tt.shape == (2, idx.size) and 0 < idx.size <= cells
+    flat = idx.astype(np.int64)
+    assert np.array_equal(flat, idx) and np.all(np.diff(flat) > 0) and flat[0] >= 0 and flat[-1] < cells
+
+    v = pkg.inputs.velocity_model(*shape, 20160507)
+    fs = pkg.inputs.make_fs(pkg.inputs.read_triples(pkg.inputs.star_path("818")))
+    starts = pkg.inputs.read_triples(pkg.inputs.starts_path("24"))[:2]
+    boxes = []
+    for st in starts:
+        box = np.full(shape, np.inf, dtype=np.float32)
+        box[tuple(st)] = 0
+        boxes.append(box)
+    with pkg.TravelTimeSolver(shape, fs) as sol:
+        sol.set_velocity(v)
+        sol.solve(starts, boxes)
+    for n, box in enumerate(boxes):
+        assert_bit_equal(tt[n], box.reshape(-1)[flat], f"dumped box {n}")

@@ -74,23 +74,24 @@ def test_quirks_change_the_answer(oracle, golden24):
 
 
 def test_against_live_reference(oracle):
-    """Fresh random inputs through the reference build (only beside /root/reference)."""
-    if oracle.ref() is None:
-        pytest.skip("reference checkout not present (GPU box)")
-    rng = np.random.default_rng(7)
-    for shape in ((13, 9, 8), (6, 17, 10)):
-        v = rng.uniform(0.1, 0.4, size=shape).astype(np.float32)
-        for n_off in (5, 40):
-            offs = rng.integers(-3, 4, size=(n_off, 3)).astype(np.int32)
-            offs = offs[np.any(offs != 0, axis=1)]
-            start = [int(rng.integers(0, n)) for n in shape]
-            (want,), ref_sweeps = oracle.ref_converge(v, offs, [start])
-            fs = oracle.make_star(offs)
-            tt, sweeps, _ = oracle.converge(v, fs, start)
-            assert sweeps == ref_sweeps
-            assert_bit_equal(tt, want, f"{shape} {n_off}")
-            tt8, _, _ = oracle.converge(v, fs, start, order=1)
-            assert_bit_equal(tt8, want, f"{shape} {n_off} 8-ord")
+    """Random inputs through the reference: its converged boxes and sweep counts as recorded in
+    tests/golden/live_ref.npz (make_golden.py), and, beside the reference checkout, fresh from its build."""
+    z = np.load(os.path.join(GOLDEN, "live_ref.npz"))
+    meta = json.loads(bytes(z["meta"]).decode())
+    assert len(meta) == 4
+    for n, m in meta.items():
+        v, offs, start = z[f"v_{n}"], z[f"offs_{n}"], [int(x) for x in z[f"start_{n}"]]
+        want, ref_sweeps = z[f"tt_{n}"], m["sweeps"]
+        if oracle.ref() is not None:
+            (live,), live_sweeps = oracle.ref_converge(v, offs, [start])
+            assert live_sweeps == ref_sweeps
+            assert_bit_equal(live, want, f"case {n}: live reference vs recorded")
+        fs = oracle.make_star(offs)
+        tt, sweeps, _ = oracle.converge(v, fs, start)
+        assert sweeps == ref_sweeps
+        assert_bit_equal(tt, want, f"{v.shape} {len(offs)}")
+        tt8, _, _ = oracle.converge(v, fs, start, order=1)
+        assert_bit_equal(tt8, want, f"{v.shape} {len(offs)} 8-ord")
 
 
 def test_vbox_checksum_matches_reference_writer(oracle):

@@ -3,7 +3,7 @@
 # parity smoke test of every build (tools/exp/check_lib.py), then the headline, the 3-start shard and the 512 grid.
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/ab; mkdir -p $O
-B="python bench.py --no-cpu --no-traffic --no-host --no-hbm-regime"
+B="python bench.py --full --no-cpu --no-traffic --no-host --no-hbm-regime"
 for name in "$@"; do
   lib=""; [ "$name" != default ] && lib="--lib gpurun_exp/$name.so"
   if [ "$name" != default ]; then timeout -k 10 200 python tools/exp/check_lib.py gpurun_exp/$name.so 2>&1 | tail -n 1; fi

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of builds on the TILE workloads: bash tools/exp/abtile.sh NAME [NAME ...]  ("default" = csrc/libttsweep.so)
 cd "${GRAFT_REPO_ROOT:-.}"
-B="python bench.py --no-cpu --no-traffic --no-host --no-hbm-regime --star six"
+B="python bench.py --full --no-cpu --no-traffic --no-host --no-hbm-regime --star six"
 for name in "$@"; do
   lib=""; [ "$name" != default ] && lib="--lib gpurun_exp/$name.so"
   for cfg in "g1024:--grid 1024,1024,512 --starts 111 --nstarts 14 --steps 2 --warmup 1" "g512:--grid 512,512,256 --starts 111 --nstarts 8 --steps 3 --warmup 1" "g241:--steps 5 --warmup 1"; do

@@ -2,7 +2,7 @@
 # 818-FS on 512x512x256 x 8 starts (one launch per solve): gate per round x deferral margin
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/g512k; mkdir -p $O
-B="python bench.py --no-cpu --no-host --no-traffic --no-hbm-regime --grid 512,512,256 --starts 111 --nstarts 8 --steps 1 --warmup 1"
+B="python bench.py --full --no-cpu --no-host --no-traffic --no-hbm-regime --grid 512,512,256 --starts 111 --nstarts 8 --steps 1 --warmup 1"
 for cfg in "$@"; do
   g=${cfg%%:*}; m=${cfg#*:}
   timeout -k 10 300 $B --async-gate $g --defer-margin $m > $O/${g}_$m.json 2> $O/${g}_$m.err || { echo "$cfg FAILED"; tail -3 $O/${g}_$m.err; exit 1; }

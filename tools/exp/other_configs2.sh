@@ -2,7 +2,7 @@
 # The other BASELINE configurations (818-FS) and the small shards, one launch per solve against a launch pair per pass.
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/oc2; mkdir -p $O
-B="python bench.py --no-cpu --no-host --no-traffic --no-hbm-regime"
+B="python bench.py --full --no-cpu --no-host --no-traffic --no-hbm-regime"
 for mode in 1 0; do
   for cfg in "n24:--steps 5 --warmup 1" "n3:--steps 5 --warmup 2 --nstarts 3" "n1:--steps 5 --warmup 2 --nstarts 1" "start4:--starts 4 --steps 5 --warmup 2" \
              "g512:--grid 512,512,256 --starts 111 --nstarts 8 --steps 2 --warmup 1" "g1024:--grid 1024,1024,512 --starts 111 --nstarts 14 --steps 1 --warmup 1"; do

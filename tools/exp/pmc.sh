@@ -9,7 +9,7 @@ name=$1; bargs=$2; pat=$3; shift 3
 export TMPDIR=/tmp
 out=gpurun_out/pmc_$name; mkdir -p "$out"
 timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$out" -- \
-    python3 bench.py --no-cpu --no-traffic --no-host $bargs > "$out.log" 2>&1 || { echo "pmc $name failed"; exit 1; }
+    python3 bench.py --full --no-cpu --no-traffic --no-host $bargs > "$out.log" 2>&1 || { echo "pmc $name failed"; exit 1; }
 python3 - "$out" "$pat" <<'PY'
 import collections, csv, glob, sys
 tot, n = collections.defaultdict(float), collections.Counter()

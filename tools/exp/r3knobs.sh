@@ -2,7 +2,7 @@
 # schedule knobs re-measured after the round-3 changes (gate speed, units of one / two planes)
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/r3knobs; rm -rf $O; mkdir -p $O
-B="python bench.py --no-cpu --no-traffic --no-host --no-hbm-regime --steps 5 --warmup 1"
+B="python bench.py --full --no-cpu --no-traffic --no-host --no-hbm-regime --steps 5 --warmup 1"
 run() { name=$1; shift; $B "$@" > $O/$name.json 2> $O/$name.err; python3 - "$O/$name.json" "$name" <<'PY'
 import json,sys
 try:

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 O=gpurun_out/r4_inunit.txt; : > $O
-B="python bench.py --no-cpu --no-traffic --no-host --no-hbm-regime --steps 4 --warmup 1"
+B="python bench.py --full --no-cpu --no-traffic --no-host --no-hbm-regime --steps 4 --warmup 1"
 run() {   # name, args...
   name=$1; shift
   for k in 0 1 2 3; do

@@ -3,7 +3,7 @@
 # one-launch STRIP solve's counts of units that improved nothing (with the deferral), the column kernel's phase profile
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r4_other; mkdir -p $O
-B="python bench.py --no-cpu --no-host --no-hbm-regime"
+B="python bench.py --full --no-cpu --no-host --no-hbm-regime"
 $B --steps 3 --warmup 1 --nstarts 3 > $O/n3.json 2> $O/n3.err; echo "n3 rc $?"
 $B --steps 3 --warmup 1 --nstarts 1 > $O/n1.json 2> $O/n1.err; echo "n1 rc $?"
 $B --steps 3 --warmup 1 --starts 4 > $O/start4.json 2> $O/start4.err; echo "start4 rc $?"

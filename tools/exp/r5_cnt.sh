@@ -9,7 +9,7 @@ for lib in "" gpurun_exp/cnt0.so; do
 done
 echo "== prof 24 starts" >> $O
 REPS=2 TTSWEEP_LIB=gpurun_exp/stripprof.so timeout -k 10 200 python tools/exp/r5_sweep.py 24 - 2>&1 | grep -E "^prof" | tail -1 >> $O
-B="python bench.py --no-cpu --no-host --no-traffic --no-hbm-regime"
+B="python bench.py --full --no-cpu --no-host --no-traffic --no-hbm-regime"
 for lib in "" "--lib gpurun_exp/cnt0.so"; do
   timeout -k 10 400 $B --grid 512,512,256 --starts 111 --nstarts 8 --steps 2 --warmup 1 $lib > gpurun_out/cnt512.json 2> gpurun_out/cnt512.err
   python3 - gpurun_out/cnt512.json "512x512x256 x 8 $lib" >> $O <<'PY'

@@ -7,12 +7,12 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 part=${1:-abc}
 O=gpurun_out/r5final; mkdir -p $O
-B="python bench.py --no-cpu --no-traffic --no-host --no-hbm-regime"
+B="python bench.py --full --no-cpu --no-traffic --no-host --no-hbm-regime"
 if [[ $part == *a* ]]; then
 echo "== default bench line (traffic passes, host program, CPU legs, HBM-regime run)"
-timeout -k 10 900 python bench.py > $O/bench_line.json 2> $O/bench_line.err; echo "rc=$?"
+timeout -k 10 900 python bench.py --full > $O/bench_line.json 2> $O/bench_line.err; echo "rc=$?"
 echo "== kernel stats of the default workload"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 5 --warmup 2 --no-cpu --no-traffic --no-host --no-hbm-regime > $O/prof_line.json 2> $O/prof.err; echo "rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-traffic --no-host --no-hbm-regime > $O/prof_line.json 2> $O/prof.err; echo "rc=$?"
 find $O/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/bench_kernel_stats.csv
 rm -rf $O/prof
 echo "== the small shards (818-FS)"
@@ -37,11 +37,11 @@ done
 fi
 if [[ $part == *b* ]]; then
 echo "== HBM regime: six-FS 1024x1024x512 x 14, line with live traffic + kernel stats"
-timeout -k 10 600 python bench.py --star six --grid 1024,1024,512 --starts 111 --nstarts 14 --steps 3 --warmup 1 --no-cpu --no-host > $O/six1024_bench_line.json 2> $O/six1024.err; echo "rc=$?"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof6 -- python3 bench.py --star six --grid 1024,1024,512 --starts 111 --nstarts 14 --steps 3 --warmup 1 --no-cpu --no-host --no-traffic > $O/six1024_prof_line.json 2> $O/six1024_prof.err; echo "rc=$?"
+timeout -k 10 600 python bench.py --full --star six --grid 1024,1024,512 --starts 111 --nstarts 14 --steps 3 --warmup 1 --no-cpu --no-host > $O/six1024_bench_line.json 2> $O/six1024.err; echo "rc=$?"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof6 -- python3 bench.py --full --star six --grid 1024,1024,512 --starts 111 --nstarts 14 --steps 3 --warmup 1 --no-cpu --no-host --no-traffic > $O/six1024_prof_line.json 2> $O/six1024_prof.err; echo "rc=$?"
 find $O/prof6 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/six1024_kernel_stats.csv
 rm -rf $O/prof6
-timeout -k 10 300 python bench.py --star six --grid 512,512,256 --starts 111 --nstarts 8 --steps 3 --warmup 1 --no-cpu --no-host > $O/six512_bench_line.json 2> $O/six512.err; echo "rc=$?"
+timeout -k 10 300 python bench.py --full --star six --grid 512,512,256 --starts 111 --nstarts 8 --steps 3 --warmup 1 --no-cpu --no-host > $O/six512_bench_line.json 2> $O/six512.err; echo "rc=$?"
 echo "== one ordering sweep with every tile due (a converged box solved again)"
 timeout -k 10 300 python tools/exp/one_sweep.py 1024,1024,512 14 > $O/six_full_sweep.txt 2>&1; echo "rc=$?"
 echo "== where the column wavefronts' time goes (-DTTSWEEP_COL_PROFILE build)"
@@ -59,7 +59,7 @@ rm -rf gpurun_out/pmc_r5sq1 gpurun_out/pmc_r5sq2 gpurun_out/pmc_r5sq3 gpurun_out
 fi
 if [[ $part == *c* ]]; then
 echo "== the other configurations (818-FS) with HBM-side traffic"
-B2="python bench.py --no-cpu --no-host --no-hbm-regime"
+B2="python bench.py --full --no-cpu --no-host --no-hbm-regime"
 $B2 --steps 2 --warmup 1 --grid 512,512,256 --starts 111 --nstarts 8 > $O/g512_818.json 2> $O/g512_818.err; echo "g512 rc $?"
 timeout -k 10 500 $B2 --steps 1 --warmup 1 --grid 1024,1024,512 --starts 111 --nstarts 14 > $O/g1024_818.json 2> $O/g1024_818.err; echo "g1024 rc $?"
 fi
