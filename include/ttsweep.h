@@ -202,7 +202,11 @@ int ttsweep_warmup(int device);
  * fs[starstart .. starstop-1] (EXCLUSIVE upper bound, as the reference call
  * site passes starsize-1, :160).  Uploads the star to `device`.
  * Replaces: the globals fs[] / nx,ny,nz and the (starstart, starstop)
- * arguments of sweepXYZ (:198).  Returns NULL on failure. */
+ * arguments of sweepXYZ (:198).  Every length fs[l].d, starstart <= l < starstop,
+ * must be finite and >= 0 (a negative, infinite or NaN length is refused: NULL, with a
+ * message).  A length whose half is not a float (a subnormal d with an odd last bit)
+ * is accepted; every volume is then solved by the per-cell kernel's instance that
+ * rounds as the reference does (see ttsweep_set_velocity).  Returns NULL on failure. */
 ttsweep_ctx *ttsweep_create(int device, int nx, int ny, int nz,
                             const ttsweep_fs *fs, int starstart, int starstop);
 void ttsweep_destroy(ttsweep_ctx *ctx);
@@ -219,7 +223,11 @@ int ttsweep_set_option(ttsweep_ctx *ctx, int key, long long value);
  * "/ 2.0" of the rounded product (:216) and the fast kernels' multiplication by d / 2 no
  * longer agree in the last bit, so such a volume goes to the per-cell kernel's instance that
  * rounds as the reference does (ttsweep_stats.kernel_variant reads TTSWEEP_KERNEL_CELL, whatever
- * TTSWEEP_OPT_KERNEL asked for; the next volume without such values gets the chosen kernel back). */
+ * TTSWEEP_OPT_KERNEL asked for; the next volume without such values gets the chosen kernel back).
+ * The high end likewise: a volume with a value >= 2^126 / (largest fs[].d of the star) - about
+ * 8.5e36 for delta 10 and the 6-neighbour star - goes to that instance, since there the
+ * reference's product d * (v[c] + v[o]) can overflow to INFINITY where d / 2 times the sum
+ * does not (the pair's delay is then INFINITY, and so is what it offers). */
 int ttsweep_set_velocity(ttsweep_ctx *ctx, const float *v_host);
 int ttsweep_set_velocity_device(ttsweep_ctx *ctx, const float *v_dev);
 
@@ -230,6 +238,10 @@ int ttsweep_set_velocity_device(ttsweep_ctx *ctx, const float *v_dev);
  *                the initial state and overwritten with the converged state.
  * Returns 1 if any travel time improved, 0 if every box was already converged
  * (the two outcomes `anychange != 0` / `== 0` of :163-166), < 0 on error.
+ * Where travel times overflow, a finite cell beside an INFINITY one stores
+ * delay + t = INFINITY over INFINITY in every reference pass (:228-237): the reference's
+ * loop never ends.  The library returns the boxes at which that loop stands still (every
+ * later pass leaves every bit as it is), and a solve of those boxes returns 0.
  * Replaces: the whole `while (anychange)` loop of :151-170 over all starts.
  * A call with exactly the arrays and starts of the previous successful call on this context,
  * their contents bit for bit as that call left them (checked with a 128-bit digest of every
@@ -257,8 +269,9 @@ int ttsweep_get_changed(const ttsweep_ctx *ctx, int *out, int n);
 /* On-device fixed-point check in the spirit of testconvergence
  * (old/wavefront-openmp/wave-multistart.c:300-347) on serial_new's edge set:
  *   open_edges         (cell, offset) pairs through which one more reference sweep would
- *                      still store (serial_new/...:219-249, evaluated without modifying
- *                      the box): 0 iff nothing can improve any more;
+ *                      still store a different value (serial_new/...:219-249, evaluated
+ *                      without modifying the box; a store of INFINITY over INFINITY, see
+ *                      ttsweep_solve, is not counted): 0 iff nothing can improve any more;
  *   cells_infinite     cells still at INFINITY;
  *   cells_unsupported  cells (other than the start) whose travel time is smaller than
  *                      every candidate their live edges offer, i.e. that no store of

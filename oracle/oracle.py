@@ -96,6 +96,8 @@ def ref():
         L.ttref_tt.restype = C.POINTER(C.c_float)
         L.ttref_fs_d.argtypes = [C.c_int]
         L.ttref_fs_d.restype = C.c_float
+        L.ttref_set_fs_d.argtypes = [C.c_int, C.c_float]
+        L.ttref_set_fs_d.restype = None
         L.ttref_store_vbox.argtypes = [C.c_char_p] + [C.c_int] * 6 + [_fp]
         L.ttref_store_vbox.restype = C.c_int
         L.ttref_load_vbox.argtypes = [C.c_char_p, _ip, _fp, C.c_long]

@@ -84,6 +84,10 @@ int ttref_sweep_default(int s)
 float *ttref_tt(int s) { return ttboxes[s].flat; }
 float ttref_fs_d(int l) { return fs[l].d; }
 
+/* A hand-made length, for a star the reference main() could not prepare
+ * (the same offset twice with two lengths); call after ttref_setup. */
+void ttref_set_fs_d(int l, float d) { fs[l].d = d; }
+
 /* Reference VBOX I/O (include/velocityboxfiler.h) for file-format pinning. */
 int ttref_store_vbox(const char *filename, int ox, int oy, int oz,
                      int nx, int ny, int nz, const float *v)

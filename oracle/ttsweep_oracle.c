@@ -33,10 +33,13 @@ void oracle_tt_init(float *tt, int nx, int ny, int nz, int si, int sj, int sk)
 }
 
 /* The relaxation of one (cell, offset) pair: serial_new/...:208-249.
- * Returns the number of stores (0 or 1). */
+ * Returns the number of stores (0 or 1); *changed counts the stores that change
+ * a value.  Every store of the both-finite branch does; a store of the one-side
+ * branches (:228-237) does not when delay + t overflows to INFINITY, which is
+ * stored over INFINITY. */
 static inline int relax_pair(const float *v, float *tt, int nx, int ny, int nz,
                              const struct oracle_fs *f, int i, int j, int k,
-                             int si, int sj, int sk)
+                             int si, int sj, int sk, long *changed)
 {
     int oi = i + f->i, oj = j + f->j, ok = k + f->k;
     size_t c, o;
@@ -63,41 +66,30 @@ static inline int relax_pair(const float *v, float *tt, int nx, int ny, int nz,
     if (t == INFINITY && to == INFINITY) return 0;              /* :225-227 */
     if (t != INFINITY && to == INFINITY) {                      /* :228-232 */
         tt[o] = delay + t;
+        *changed += tt[o] != INFINITY;
         return 1;
     }
     if (t == INFINITY && to != INFINITY) {                      /* :233-237 */
         tt[c] = delay + to;
+        *changed += tt[c] != INFINITY;
         return 1;
     }
     /* :238-249 both finite */
     if ((delay + to) < t) {
         tt[c] = delay + to;
+        ++*changed;
         return 1;
     } else if ((delay + t) < to) {
         tt[o] = delay + t;
+        ++*changed;
         return 1;
     }
     return 0;
 }
 
-/* serial_new/sweep-tt-multistart.c:198-256 */
-long oracle_sweepXYZ(const float *v, float *tt, int nx, int ny, int nz,
-                     const struct oracle_fs *fs, int starstart, int starstop,
-                     int si, int sj, int sk)
-{
-    long change = 0;
-    int i, j, k, l;
-    for (i = 0; i < nx; i++)
-        for (j = 0; j < ny; j++)
-            for (k = 0; k < nz; k++)
-                for (l = starstart; l < starstop; l++)
-                    change += relax_pair(v, tt, nx, ny, nz, &fs[l], i, j, k, si, sj, sk);
-    return change;
-}
-
-long oracle_sweep_dir(const float *v, float *tt, int nx, int ny, int nz,
+static long sweep_dir(const float *v, float *tt, int nx, int ny, int nz,
                       const struct oracle_fs *fs, int starstart, int starstop,
-                      int si, int sj, int sk, int dirx, int diry, int dirz)
+                      int si, int sj, int sk, int dirx, int diry, int dirz, long *changed)
 {
     long change = 0;
     int a, b, c, l;
@@ -108,15 +100,34 @@ long oracle_sweep_dir(const float *v, float *tt, int nx, int ny, int nz,
             for (c = 0; c < nz; c++) {
                 int k = dirz >= 0 ? c : nz - 1 - c;
                 for (l = starstart; l < starstop; l++)
-                    change += relax_pair(v, tt, nx, ny, nz, &fs[l], i, j, k, si, sj, sk);
+                    change += relax_pair(v, tt, nx, ny, nz, &fs[l], i, j, k, si, sj, sk, changed);
             }
         }
     }
     return change;
 }
 
+/* serial_new/sweep-tt-multistart.c:198-256 */
+long oracle_sweepXYZ(const float *v, float *tt, int nx, int ny, int nz,
+                     const struct oracle_fs *fs, int starstart, int starstop,
+                     int si, int sj, int sk)
+{
+    long changed = 0;
+    return sweep_dir(v, tt, nx, ny, nz, fs, starstart, starstop, si, sj, sk, 1, 1, 1, &changed);
+}
+
+long oracle_sweep_dir(const float *v, float *tt, int nx, int ny, int nz,
+                      const struct oracle_fs *fs, int starstart, int starstop,
+                      int si, int sj, int sk, int dirx, int diry, int dirz)
+{
+    long changed = 0;
+    return sweep_dir(v, tt, nx, ny, nz, fs, starstart, starstop, si, sj, sk, dirx, diry, dirz,
+                     &changed);
+}
+
 /* serial_new/...:151-170 minus the break at :168-169
- * (= old/sweep-serial/sweep-tt-multistart.c:189-211), one start */
+ * (= old/sweep-serial/sweep-tt-multistart.c:189-211), one start, ending at the
+ * first pass that changes no value (see ttsweep_oracle.h) */
 int oracle_converge(const float *v, float *tt, int nx, int ny, int nz,
                     const struct oracle_fs *fs, int starstart, int starstop,
                     int si, int sj, int sk, int order, int max_sweeps,
@@ -125,19 +136,17 @@ int oracle_converge(const float *v, float *tt, int nx, int ny, int nz,
     int sweeps = 0;
     long total = 0, changed;
     do {
+        long stores;
         if (max_sweeps > 0 && sweeps >= max_sweeps) {
             if (stores_out) *stores_out = total;
             return -1;
         }
-        if (order == 0) {
-            changed = oracle_sweepXYZ(v, tt, nx, ny, nz, fs, starstart, starstop, si, sj, sk);
-        } else {
-            int m = sweeps & 7;
-            changed = oracle_sweep_dir(v, tt, nx, ny, nz, fs, starstart, starstop, si, sj, sk,
-                                       (m & 1) ? -1 : 1, (m & 2) ? -1 : 1, (m & 4) ? -1 : 1);
-        }
+        int m = order == 0 ? 0 : sweeps & 7;
+        changed = 0;
+        stores = sweep_dir(v, tt, nx, ny, nz, fs, starstart, starstop, si, sj, sk,
+                           (m & 1) ? -1 : 1, (m & 2) ? -1 : 1, (m & 4) ? -1 : 1, &changed);
         sweeps++;
-        total += changed;
+        total += stores;
     } while (changed);
     if (stores_out) *stores_out = total;
     return sweeps;
@@ -167,8 +176,9 @@ long oracle_validate(const float *v, const float *tt, int nx, int ny, int nz,
                     delay = (float)((double)prod / 2.0);
                     t = tt[c];
                     to = tt[o];
-                    if (t == INFINITY && to == INFINITY) continue;
-                    if (t == INFINITY || to == INFINITY) { open++; continue; }
+                    /* a store that would change a value: with t (or to) at INFINITY,
+                     * the one-side branches (:228-237) store delay + to (or t),
+                     * which changes it iff that is finite, i.e. below INFINITY */
                     if ((delay + to) < t || (delay + t) < to) open++;
                 }
             }

@@ -57,14 +57,18 @@ long oracle_sweep_dir(const float *v, float *tt, int nx, int ny, int nz,
                       const struct oracle_fs *fs, int starstart, int starstop,
                       int si, int sj, int sk, int dirx, int diry, int dirz);
 
-/* Driver loop: sweep until a pass makes no store (the `while (anychange)` loop
+/* Driver loop: sweep until a pass changes no value (the `while (anychange)` loop
  * of serial_new/sweep-tt-multistart.c:151-170 without the temporary `break` at
  * :168-169, i.e. old/sweep-serial/sweep-tt-multistart.c:189-211), for ONE start.
+ * Outside overflow every store changes a value and this is the reference's own
+ * exit.  Where a travel time overflows, a finite cell next to an INFINITY one
+ * stores delay + t = INFINITY over INFINITY in every pass (:228-237): the
+ * reference's loop never ends, this one ends at the box it stands still at.
  * order = 0: reference order every pass; order = 1: cycle through the 8
  * (+-x,+-y,+-z) orderings.  Stops after max_sweeps passes if > 0.
- * Returns the number of passes executed (the last one being the all-quiet
- * pass), or -1 if max_sweeps was hit first.  *stores_out (may be NULL)
- * receives the total number of stores. */
+ * Returns the number of passes executed (the last one being the pass that
+ * changes nothing), or -1 if max_sweeps was hit first.  *stores_out (may be
+ * NULL) receives the total number of stores, that last pass's included. */
 int oracle_converge(const float *v, float *tt, int nx, int ny, int nz,
                     const struct oracle_fs *fs, int starstart, int starstop,
                     int si, int sj, int sk, int order, int max_sweeps,
@@ -72,8 +76,9 @@ int oracle_converge(const float *v, float *tt, int nx, int ny, int nz,
 
 /* Fixed-point check in the spirit of testconvergence
  * (old/wavefront-openmp/wave-multistart.c:300-347) but on serial_new's edge
- * set: counts the (cell, offset) pairs a further reference sweep would still
- * store through, without modifying tt.  *ninf_out (may be NULL) receives the
+ * set: counts the (cell, offset) pairs through which a further reference sweep
+ * would still store a different value, without modifying tt (a store of
+ * INFINITY over INFINITY, see oracle_converge, is not counted).  *ninf_out (may be NULL) receives the
  * number of cells still at INFINITY.  0 means converged. */
 long oracle_validate(const float *v, const float *tt, int nx, int ny, int nz,
                      const struct oracle_fs *fs, int starstart, int starstop,

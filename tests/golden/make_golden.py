@@ -9,6 +9,7 @@ records inputs and the reference's outputs.  The fixtures are data only
 
   python tests/golden/make_golden.py            # small fixtures (seconds)
   python tests/golden/make_golden.py --big      # + 241x241x51 digests (minutes)
+  python tests/golden/make_golden.py --float-range   # float_range.npz only (seconds)
 """
 import argparse
 import hashlib
@@ -155,6 +156,139 @@ def live_fixture():
     print("live_ref cases:", len(meta))
 
 
+# ---------------------------------------------------------------------------
+# the ends of the float range (float_range.npz)
+# ---------------------------------------------------------------------------
+
+# 0x116c3: a subnormal star length whose half is not a float (odd last bit); 0x116c4 is the next
+# length up, and both halve to the same float
+ODD_SUBNORMAL = int(0x116c3)
+
+
+def f32_bits(b):
+    return np.array([b], np.uint32).view(np.float32)[0]
+
+
+def asym_star():
+    """A random, not point-symmetric star of radius 2 (12 distinct non-zero offsets; the last one
+    is the entry the reference's exclusive bound leaves out)."""
+    rng = np.random.default_rng(4242)
+    offs = []
+    while len(offs) < 12:
+        o = tuple(int(x) for x in rng.integers(-2, 3, size=3))
+        if o != (0, 0, 0) and o not in offs and tuple(-x for x in o) not in offs:
+            offs.append(o)
+    return np.array(offs, np.int32)
+
+
+def dup_star():
+    """The 6-neighbour shell at length 0x116c4 with +x a second time at 0x116c3 (one subnormal step
+    shorter: the shorter edge is the one that counts), and a sacrificial last entry."""
+    offs = np.concatenate([SIX[:6], [[1, 0, 0]], SIX[6:]]).astype(np.int32)
+    d = np.full(len(offs), 0x116c4, np.uint32)
+    d[6] = ODD_SUBNORMAL
+    d[-1] = 0
+    return offs, d
+
+
+def float_range_cases():
+    """(case, shape, v, delta, star names, starts).  Stars: "six" (the shipped 6-FS), "5" (5-FS),
+    "asym" (asym_star), "dup" (dup_star, with its own lengths)."""
+    rng = np.random.default_rng(2026)
+
+    def logu(lo, hi, shape):
+        return (10.0 ** rng.uniform(np.log10(lo), np.log10(hi), size=shape)).astype(np.float32)
+
+    every = ("six", "5", "asym")
+    cases = []
+    # (a) travel times overflow partway across the grid; delays finite
+    shape = (16, 14, 12)
+    cases.append(("overflow_tt", shape, logu(2e36, 1.6e37, shape), 10.0, every,
+                  [(8, 7, 6), (0, 0, 0), (15, 2, 11)]))
+    # ... and the same below 2^126 / d_max (six: 8.5e36, asym: 2.5e36), where the fast kernels stay
+    cases.append(("overflow_tt_fast", shape, logu(1.2e36, 2.4e36, shape), 10.0, ("six", "asym"),
+                  [(8, 7, 6), (0, 13, 0)]))
+    # (b) the band where d (v[c] + v[o]) overflows while d / 2 (v[c] + v[o]) does not (for d = 10:
+    # sums in [3.4e37, 6.8e37)), around a start in a slower region
+    shape = (12, 10, 9)
+    v = logu(1.2e37, 3.4e37, shape)
+    v[4:8, 3:7, 3:6] = logu(1e35, 1e36, (4, 4, 3))
+    cases.append(("overflow_delay", shape, v, 10.0, every, [(6, 5, 4), (0, 9, 8)]))
+    # (c) blocks where the pair sum itself is infinite; one start inside one of them
+    shape = (14, 12, 10)
+    v = synth(*shape, 11)
+    v[2:6, 3:9, 1:5] = logu(1.8e38, 3.4e38, (4, 6, 4))
+    v[9:13, 0:4, 6:10] = np.float32(3.4028235e38)
+    cases.append(("inf_sum", shape, v, 10.0, every, [(7, 6, 5), (3, 5, 2)]))
+    # (d) a star length with an inexact half: ordinary velocities (denormal delays) and v ~ 1e30
+    shape = (12, 10, 9)
+    odd = float(f32_bits(ODD_SUBNORMAL))
+    cases.append(("odd_delta", shape, synth(*shape, 12), odd, every, [(6, 5, 4), (0, 0, 0)]))
+    cases.append(("odd_delta_1e30", shape, logu(1e30, 3e30, shape), odd, every, [(6, 5, 4), (11, 0, 8)]))
+    # (e) ordinary lengths other than delta = 10
+    cases.append(("delta_0.37", shape, synth(*shape, 13), 0.37, every, [(6, 5, 4), (0, 9, 0)]))
+    cases.append(("delta_2500", shape, synth(*shape, 14), 2500.0, every, [(6, 5, 4), (11, 9, 8)]))
+    # (f) the same offset twice, lengths one subnormal step apart
+    cases.append(("dup_offset", shape, logu(1e30, 3e30, shape), 10.0, ("dup",), [(6, 5, 4), (0, 3, 2)]))
+    return cases
+
+
+def ref_fixed_point(v, offs, fs_d_bits, delta, start, max_passes=2000):
+    """Step the reference's own sweepXYZ (call-site bounds, :160) one pass at a time up to the first
+    pass that changes no bit.  Returns (box, passes, stores of that last pass, the reference's fs[].d
+    bits).  Where a travel time overflows, that pass still stores (INFINITY over INFINITY) and the
+    reference's own loop would go on for ever."""
+    R = O.ref()
+    shape = v.shape
+    st = np.asarray(start, np.int32)
+    assert R.ttref_setup(*shape, np.ascontiguousarray(v).reshape(-1), len(offs),
+                         np.ascontiguousarray(offs).reshape(-1).copy(), np.float32(delta), 1, st.copy())
+    if fs_d_bits is not None:
+        for l, b in enumerate(fs_d_bits):
+            R.ttref_set_fs_d(l, f32_bits(b))
+    d_bits = np.array([R.ttref_fs_d(l) for l in range(len(offs))], np.float32).view(np.uint32)
+    tt = np.ctypeslib.as_array(R.ttref_tt(0), shape=shape)
+    passes = 0
+    while True:
+        before = tt.copy()
+        stores = R.ttref_sweep(0, 0, len(offs) - 1)
+        passes += 1
+        if np.array_equal(before.view(np.uint32), tt.view(np.uint32)):
+            break
+        assert passes < max_passes
+    box = tt.copy()
+    R.ttref_teardown()
+    return box, passes, int(stores), d_bits
+
+
+def float_range_fixture():
+    """tests/golden/float_range.npz: the reference's fixed points at both ends of the float range."""
+    star_offs = {"six": SIX, "5": shipped("5"), "asym": asym_star(), "dup": dup_star()[0]}
+    out = {f"star_{k}": o for k, o in star_offs.items()}
+    meta = {}
+    for case, shape, v, delta, snames, starts in float_range_cases():
+        out[f"v_{case}"] = v
+        for sname in snames:
+            key = f"{case}/{sname}"
+            d_in = dup_star()[1] if sname == "dup" else None
+            boxes, rec = [], {"case": case, "star": sname, "starts": [list(s) for s in starts],
+                              "delta_bits": int(np.float32(delta).view(np.uint32)),
+                              "hand_made_d": d_in is not None, "passes": [], "last_stores": []}
+            for st in starts:
+                box, passes, stores, d_bits = ref_fixed_point(v, star_offs[sname], d_in, delta, st)
+                boxes.append(box)
+                rec["passes"].append(passes)
+                rec["last_stores"].append(stores)
+            rec["ninf"] = [int(np.isinf(b).sum()) for b in boxes]
+            out[f"tt_{key}"] = np.stack(boxes)
+            out[f"fsd_{key}"] = d_bits
+            meta[key] = rec
+            print(key, "passes", rec["passes"], "last-pass stores", rec["last_stores"], "INF cells", rec["ninf"])
+    out["meta"] = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), dtype=np.uint8)
+    np.savez_compressed(os.path.join(HERE, "float_range.npz"), **out)
+    print("float_range cases:", len(meta), os.path.getsize(os.path.join(HERE, "float_range.npz")), "bytes")
+
+
 def big_digests():
     """Converged 241x241x51 boxes of the reference: SHA-256 + spot values only."""
     v = synth(241, 241, 51, 20160507)
@@ -215,6 +349,7 @@ if __name__ == "__main__":
     ap.add_argument("--big-file", default="24")
     ap.add_argument("--big-star", default="818")
     ap.add_argument("--merge-big", action="store_true")
+    ap.add_argument("--float-range", action="store_true")
     args = ap.parse_args()
     if args.big_start is not None:
         big_start24(args.big_start, args.big_file, args.big_star)
@@ -224,6 +359,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if O.ref() is None:
         sys.exit("reference not available: golden vectors can only be generated beside /root/reference")
+    if args.float_range:
+        float_range_fixture()
+        sys.exit(0)
     small_fixtures()
     vbox_fixture()
     live_fixture()

@@ -3,9 +3,12 @@ ops on the device; no code shared with libttsweep.so).  It restates the store co
 serial_new/sweep-tt-multistart.c:219-249 for a whole box at once:
 
   open_edges   (cell c, entry l < L) pairs, c != start, c + off[l] inside the grid, through which
-               one more reference sweep would still store: exactly one of T[c], T[o] infinite,
-               or delay + T[o] < T[c], or delay + T[c] < T[o], with
-               delay = fl(fl(d_l * fl(v[c] + v[o])) / 2)   (:216; eager ops round separately)
+               one more reference sweep would still store a different value:
+               delay + T[o] < T[c], or delay + T[c] < T[o], with
+               delay = fl(fl(d_l * fl(v[c] + v[o])) / 2)   (:216; eager ops round separately).
+               With one side INFINITY the reference stores delay + (the finite side) (:228-237),
+               a change iff that sum is finite, i.e. below INFINITY: the same two comparisons.
+               (Where it overflows, the store writes INFINITY over INFINITY forever.)
   unsupported  cells (other than the start) whose finite travel time is below every candidate
                their live edges offer (no store of :222-223 / :246-247 can have produced it)
 
@@ -46,7 +49,7 @@ def fixed_point_counts(v: torch.Tensor, T: torch.Tensor, fs: np.ndarray, start, 
         delay = (d * (v[ci, cj, ck] + v[oi, oj, ok])) * half      # three separately rounded ops
         cand_c = delay + To                 # what c is offered through this edge
         cand_o = delay + Tc                 # what o is offered
-        opened = (cand_c < Tc) | (cand_o < To) | (torch.isinf(Tc) != torch.isinf(To))
+        opened = (cand_c < Tc) | (cand_o < To)
         # edges centred on the start are never relaxed (:219-221)
         at = (si - ci.start, sj - cj.start, sk - ck.start)
         centre_is_start = all(0 <= a < n for a, n in zip(at, Tc.shape))

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -120,6 +121,15 @@ ttsweep_ctx *ttsweep_create(int device, int nx, int ny, int nz, const ttsweep_fs
         set_error("ttsweep_create: bad arguments");
         return nullptr;
     }
+    for (int l = starstart; l < starstop; l++) {    // (delays >= 0 and no NaN: SURVEY.md section 8-a)
+        uint32_t b;                                 // (on the bits: this file is built with -fno-honor-nans)
+        std::memcpy(&b, &fs[l].d, 4);
+        if (!(b < 0x7f800000u || b == 0x80000000u)) {
+            set_error("ttsweep_create: star entry %d has length %g (a length must be finite and >= 0)", l,
+                      (double)fs[l].d);
+            return nullptr;
+        }
+    }
     int ndev = ttsweep_device_count();
     if (ndev <= 0) {
         if (ndev == 0) set_error("ttsweep_create: no HIP device (there is no CPU fallback)");
@@ -135,7 +145,8 @@ ttsweep_ctx *ttsweep_create(int device, int nx, int ny, int nz, const ttsweep_fs
     ctx->fs_copy.assign(fs, fs + starstop);
     ctx->starstart = starstart;
     ctx->starstop = starstop;
-    ctx->pull = build_pull_star(fs, starstart, starstop);
+    ctx->pull = build_pull_star(fs, starstart, starstop, &ctx->pull_d);
+    for (float d : ctx->pull_d) ctx->half_inexact |= !half_exact(d);
     ctx->radius = pull_star_radius(ctx->pull);
     ctx->gate_speed = std::max(1.0, 0.5 * ctx->radius);
     ctx->gate_r0 = ctx->radius + 1.0;
@@ -392,26 +403,34 @@ int ttsweep_set_velocity_device(ttsweep_ctx *ctx, const float *v_dev)
     // halves exactly).  A volume with a positive value below that is accepted all the same and solved
     // by the CELL kernel's EXACT instance, which rounds as the reference does (product, then half):
     // slow, but what the reference accepts the boundary accepts, with the same bits.
+    // The high end likewise: with the largest length d_max, no product d * (v[c] + v[o]) can overflow
+    // while v < 2^126 / d_max.  Above that the reference's product may be INFINITY where d / 2 times the
+    // sum is finite (tests/test_gpu_float_range.py): such volumes take the EXACT instance as well.
+    // A star with a length whose half is not a float (half_inexact) takes it for every volume.
     unsigned long long *d_bad = ctx->d_scratch, h_bad[2] = {0, 0};
     const long long n = (long long)ctx->nx * ctx->ny * ctx->nz;
     HIPCHK(hipMemsetAsync(d_bad, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    float tiny = 0.0f;
+    float tiny = 0.0f, huge = 0.0f;
     {
-        float dmin = 0.0f;
+        float dmin = 0.0f, dmax = 0.0f;
         for (int l = ctx->starstart; l < ctx->starstop; l++) {
             const float d = ctx->fs_copy[l].d;
             if (d > 0.0f && (dmin == 0.0f || d < dmin)) dmin = d;
+            dmax = std::max(dmax, d);
         }
         if (dmin > 0.0f) tiny = (float)std::min(std::ldexp(1.0, -124) / (double)dmin, 1.0e30);
+        // (a limit above the largest float: no finite value reaches it; huge = 0 stands for that)
+        if (dmax > 0.0f && std::ldexp(1.0, 126) / (double)dmax <= (double)FLT_MAX)
+            huge = (float)(std::ldexp(1.0, 126) / (double)dmax);
     }
-    HIPCHK(launch_count_bad_velocity(v_dev, n, tiny, d_bad, ctx->stream));
+    HIPCHK(launch_count_bad_velocity(v_dev, n, tiny, huge, d_bad, ctx->stream));
     HIPCHK(hipMemcpyAsync(h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (h_bad[0]) {
         ctx->have_v = false;
         return set_error("velocity volume holds %llu cells that are negative or not finite", h_bad[0]);
     }
-    const bool exact = h_bad[1] != 0;
+    const bool exact = h_bad[1] != 0 || ctx->half_inexact;
     if (exact != ctx->exact_half) {
         if (exact) {
             ctx->kernel_wanted = ctx->kernel;

@@ -53,6 +53,7 @@ struct ttsweep_ctx {
     hipStream_t stream = nullptr;
 
     std::vector<ttsweep_pull_entry> pull;   // user-axis pull star
+    std::vector<float> pull_d;              // the length d of every pull entry (h = d / 2 but for half_inexact)
     int radius = 0;
     long long relax_per_sweep = 0;
 
@@ -65,7 +66,9 @@ struct ttsweep_ctx {
     int handoff_default = 3;
     int async_handoff = -1;                     // workers publish successor units themselves (ASYNC_HANDOFF_*; -1: by the size of the solve)
     int async_inunit = -1;                      // in-unit passes of a one-launch STRIP solve (-1: by the number of starts)
-    bool exact_half = false;                    // the velocity volume holds sub-limit values: CELL kernel, reference rounding
+    bool exact_half = false;                    // the velocity volume holds values beyond the limits (or half_inexact):
+                                                // CELL kernel, reference rounding
+    bool half_inexact = false;                  // a live star length whose half is not a float: EXACT for every volume
     int kernel_wanted = 0;                      // ... and the kernel to go back to when a volume without them arrives
     unsigned long long *d_scratch = nullptr;    // four counters for one-off kernels (velocity check, validator)
     CellEntry *d_cell_entries = nullptr;

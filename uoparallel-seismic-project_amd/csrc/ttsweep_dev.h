@@ -42,13 +42,14 @@ struct CellEntry {
     int delta;
     float h;
     int flags;
-    int pad_;
+    float d;        // the length itself (h = d / 2): the EXACT instances multiply by d
 };
 
 // One forward star entry in device axes, for the validator kernel.
 struct FwdEntry {
     int da, db, dc;
     float h;
+    float d;
 };
 
 // Per-start device record.

@@ -26,14 +26,16 @@ hipError_t launch_unpack_batch(const DevLayout &L, const float *padded0, float *
 // *seen |= 1 << (XCD id) for every workgroup of an `nblocks`-workgroup launch
 hipError_t launch_xcc_census(unsigned *seen, int nblocks, hipStream_t st);
 // *bad += cells of the caller's n-cell velocity volume that are negative, not finite, or
-// positive but below `tiny` (bad[1]; bad[0]: negative, infinite, NaN)
-hipError_t launch_count_bad_velocity(const float *v, long long n, float tiny, unsigned long long *bad, hipStream_t st);
+// positive but below `tiny` or finite and >= `huge` (bad[1]; bad[0]: negative, infinite, NaN)
+hipError_t launch_count_bad_velocity(const float *v, long long n, float tiny, float huge, unsigned long long *bad,
+                                     hipStream_t st);
 
 // ---- sweep, variant CELL ---------------------------------------------------
 // One chaotic in-place pull pass over the whole grid for the `nactive` starts
 // listed in `active`; changed[s] is OR-ed with 1 when any cell of start s
 // improved.  exact: delays rounded as the reference rounds them - product first, then halved - for velocity
-// volumes whose products can be denormal numbers (ttsweep_set_velocity decides).
+// volumes whose products can be denormal numbers or overflow, and for stars with a length whose half is not a
+// float (ttsweep_set_velocity decides).
 hipError_t launch_sweep_cell(const DevLayout &L, const float *v, const StartDesc *starts,
                              const int *active, int nactive, int *changed,
                              const CellEntry *entries, int nentries, bool exact, hipStream_t st);

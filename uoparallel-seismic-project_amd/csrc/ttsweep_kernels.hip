@@ -228,17 +228,21 @@ hipError_t launch_xcc_census(unsigned *seen, int nblocks, hipStream_t st)
 // that a delay fl(d * (v[c] + v[o])) could fall into the denormal range, where halving is no
 // longer exact - the reference halves the rounded product (serial_new/...:216: "/ 2.0"), the
 // kernels multiply by d/2, and the two agree bit for bit only while the product is a normal
-// number (or zero).  Zero - either sign - is accepted as the reference accepts it.  Integer
-// tests on the bit pattern: this file is compiled with -fno-honor-nans.
+// number (or zero); and finite values at or above `huge_bits`: so large that the product could
+// overflow (the reference's delay is then INFINITY) while the kernels' d/2 times the sum does not.
+// Zero - either sign - is accepted as the reference accepts it.  Integer tests on the bit pattern:
+// this file is compiled with -fno-honor-nans.
 __global__ void __launch_bounds__(256)
-count_bad_velocity_kernel(const float *__restrict__ v, long long n, unsigned tiny_bits, unsigned long long *__restrict__ bad)
+count_bad_velocity_kernel(const float *__restrict__ v, long long n, unsigned tiny_bits, unsigned huge_bits,
+                          unsigned long long *__restrict__ bad)
 {
     unsigned mine = 0, mine_small = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const unsigned bits = __float_as_uint(v[i]);
         const bool zero = bits == 0u || bits == 0x80000000u;
-        const bool small = !zero && bits < tiny_bits;               // (positive: the sign bit makes a number large)
         const bool ok = zero || bits < 0x7f800000u;
+        const bool small = !zero && (bits < tiny_bits                // (positive: the sign bit makes a number large)
+                                     || (ok && bits >= huge_bits));
         mine += !ok;
         mine_small += small;
     }
@@ -248,12 +252,15 @@ count_bad_velocity_kernel(const float *__restrict__ v, long long n, unsigned tin
     if ((threadIdx.x & 63) == 0 && mine_small) atomicAdd(bad + 1, (unsigned long long)mine_small);
 }
 
-hipError_t launch_count_bad_velocity(const float *v, long long n, float tiny, unsigned long long *bad, hipStream_t st)
+hipError_t launch_count_bad_velocity(const float *v, long long n, float tiny, float huge, unsigned long long *bad,
+                                     hipStream_t st)
 {
     const unsigned nblocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
     unsigned tiny_bits = 1u;            // (every positive number)
     if (tiny > 0.0f) memcpy(&tiny_bits, &tiny, sizeof tiny_bits);
-    hipLaunchKernelGGL(count_bad_velocity_kernel, dim3(nblocks), dim3(256), 0, st, v, n, tiny_bits, bad);
+    unsigned huge_bits = 0x7f800000u;   // (no finite number)
+    if (huge > 0.0f) memcpy(&huge_bits, &huge, sizeof huge_bits);
+    hipLaunchKernelGGL(count_bad_velocity_kernel, dim3(nblocks), dim3(256), 0, st, v, n, tiny_bits, huge_bits, bad);
     return hipGetLastError();
 }
 
@@ -279,12 +286,14 @@ constexpr int CELL_BY = 4;      // rows of b per block
 
 // EXACT: the reference's own rounding of a delay - the product d (v[c] + v[o]) rounded, THEN halved
 // (serial_new/sweep-tt-multistart.c:216) - for velocity volumes with values so small that the product can be a
-// denormal number, where d / 2 times the sum rounds differently (h + h = d exactly).
+// denormal number, where d / 2 times the sum rounds differently; so large that the product overflows while
+// d / 2 times the sum does not (the reference's delay is then INFINITY); and for stars with a length d whose
+// half is not a float (a subnormal d with an odd last bit): hence d itself, not h + h.
 template <bool EXACT>
-__device__ __forceinline__ float edge_delay(float h, float sum)
+__device__ __forceinline__ float edge_delay(float h, float d, float sum)
 {
     if (EXACT) {
-        float p = (h + h) * sum;
+        float p = d * sum;
         asm volatile("" : "+v"(p));     // (the product is rounded before it is halved)
         return p * 0.5f;
     }
@@ -325,7 +334,7 @@ sweep_cell_kernel(DevLayout L, const float *__restrict__ v,
             const bool live = ((en.flags & PULL_FWD) && !c_is_start)
                            || ((en.flags & PULL_REV) && oi != sd.sidx);
             const float sum = vc + v[oi];
-            const float delay = edge_delay<EXACT>(en.h, sum);
+            const float delay = edge_delay<EXACT>(en.h, en.d, sum);
             const float cand = delay + T[oi];
             if (live && cand < best) best = cand;
         }
@@ -357,8 +366,10 @@ hipError_t launch_sweep_cell(const DevLayout &L, const float *v, const StartDesc
 // validator: the reference's store conditions, read-only
 // ===========================================================================
 // For every interior centre cell c != start and every forward entry (offset e, l in
-// [starstart, starstop)) with c + e inside the grid: would serial_new/...:225-249 store?
-//   exactly one of T[c], T[o] infinite, or delay + T[o] < T[c], or delay + T[c] < T[o].
+// [starstart, starstop)) with c + e inside the grid: would serial_new/...:225-249 store a
+// different value?  delay + T[o] < T[c], or delay + T[c] < T[o].  With one side INFINITY the
+// reference stores delay + (the finite side) (:228-237), a change iff that sum is finite: the
+// same comparisons (an overflowing sum is stored as INFINITY over INFINITY, for ever).
 
 template <bool EXACT>
 __global__ void __launch_bounds__(CELL_BX *CELL_BY)
@@ -387,10 +398,8 @@ validate_kernel(DevLayout L, const float *__restrict__ v, const float *__restric
                 const long long oi = dev_index(L, oa, ob, oc);
                 const float to = T[oi];
                 const float sum = vc + v[oi];
-                const float delay = edge_delay<EXACT>(en.h, sum);
-                const bool tinf = tc == __builtin_inff(), oinf = to == __builtin_inff();
-                if (tinf && oinf) continue;
-                if (tinf != oinf || delay + to < tc || delay + tc < to) open++;
+                const float delay = edge_delay<EXACT>(en.h, en.d, sum);
+                if (delay + to < tc || delay + tc < to) open++;
             }
         }
     }
@@ -435,7 +444,7 @@ support_kernel(DevLayout L, const float *__restrict__ v, const float *__restrict
                 // (ci is not the start, so PULL_FWD entries are live)
                 const bool live = (en.flags & PULL_FWD) || ((en.flags & PULL_REV) && oi != sidx);
                 const float sum = vc + v[oi];
-                const float delay = edge_delay<EXACT>(en.h, sum);
+                const float delay = edge_delay<EXACT>(en.h, en.d, sum);
                 const float cand = delay + T[oi];
                 if (live && cand < best) best = cand;
             }

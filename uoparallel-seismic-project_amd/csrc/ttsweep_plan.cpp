@@ -334,7 +334,7 @@ int upload_star(ttsweep_ctx *ctx)
         ce[e].delta = (int)delta;
         ce[e].h = p.h;
         ce[e].flags = p.flags;
-        ce[e].pad_ = 0;
+        ce[e].d = ctx->pull_d[e];
     }
     // order by address so consecutive entries touch neighbouring cache lines
     std::sort(ce.begin(), ce.end(),
@@ -342,10 +342,11 @@ int upload_star(ttsweep_ctx *ctx)
     {   // forward entries in device axes for the validator: exactly the entries whose
         // edge is centred on the cell (PULL_FWD), i.e. the reference's (cell, l) pairs
         std::vector<FwdEntry> fe;
-        for (const auto &q : ctx->pull) {
+        for (size_t e = 0; e < ctx->pull.size(); e++) {
+            const ttsweep_pull_entry &q = ctx->pull[e];
             if (!(q.flags & PULL_FWD)) continue;
             const int u[3] = {q.di, q.dj, q.dk};
-            fe.push_back(FwdEntry{u[L.perm[0]], u[L.perm[1]], u[L.perm[2]], q.h});
+            fe.push_back(FwdEntry{u[L.perm[0]], u[L.perm[1]], u[L.perm[2]], q.h, ctx->pull_d[e]});
         }
         if (ctx->d_fwd_entries) HIPCHK(hipFree(ctx->d_fwd_entries));
         ctx->d_fwd_entries = nullptr;
