@@ -285,6 +285,65 @@ int ttsweep_validate_device(ttsweep_ctx *ctx, const ttsweep_start *start, const 
                             long long *open_edges, long long *cells_infinite,
                             long long *cells_unsupported);
 
+/* ---- rays: shortest paths of converged boxes --------------------------- */
+/* The relaxation is the shortest-path (network) ray method: in a converged box every finite travel time
+ * other than the start's is delay + T[o] of a live edge from a neighbour o with a smaller T[o] (a store of
+ * serial_new/sweep-tt-multistart.c:222-223 / :246-247).  These calls read that back - the ray from each
+ * start to each receiver, the receiver's time and, through the hop lengths, one row of dt/dv per ray - for
+ * the boxes a solve produced (INTEGRATION.md "Rays").  They change no box and no state of the context: a
+ * ttsweep_solve of the same boxes afterwards is still answered without device work.  Indices are int32:
+ * grids of more than INT32_MAX cells are refused. */
+#define TTSWEEP_HAS_RAYS 1          /* the ray calls below exist (TTSWEEP_ABI_VERSION stays 6) */
+
+/* pred[s][c] values other than a cell index */
+#define TTSWEEP_PRED_SOURCE (-1)    /* c is the start of box s */
+#define TTSWEEP_PRED_SEED (-2)      /* a finite T[c] no live edge produces: a value the caller seeded (a solve with
+                                       init = 0), or a plateau of zero delays */
+#define TTSWEEP_PRED_UNREACHED (-3) /* T[c] is not below INFINITY */
+
+/* Predecessors of every cell of nstart boxes, one launch.  For box s with start S = starts[s] and cell c
+ * (FLOATBOX index x*ny*nz + y*nz + z): TTSWEEP_PRED_SOURCE if c == S, else TTSWEEP_PRED_UNREACHED if
+ * T[c] is INFINITY or NaN, else the SMALLEST FLOATBOX index o over the live pull edges of c (entry +f_l live
+ * if c != S, entry -f_l live if c - f_l != S, l in [starstart, starstop), o inside the grid) with
+ * T[o] < T[c] and fl(delay + T[o]) == T[c], where delay = fl(fl(d_l * fl(v[c] + v[o])) / 2) exactly as the
+ * solve rounds it (:216); TTSWEEP_PRED_SEED if there is none.
+ *   tt_dev[s]   : device address of box s (float, FLOATBOX layout), read only
+ *   pred_dev[s] : device address of box s's predecessors (int32, FLOATBOX layout), written
+ * Returns 0, < 0 on error (NULL arguments, a start outside the grid, no velocity set, a grid of more than
+ * INT32_MAX cells: refused before any device work).  Returns when pred is written. */
+int ttsweep_predecessors_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                const float *const *tt_dev, int *const *pred_dev);
+
+/* status of a ray */
+#define TTSWEEP_RAY_OK 0            /* the path ends at the start */
+#define TTSWEEP_RAY_SEED 1          /* the path ends at a TTSWEEP_PRED_SEED cell */
+#define TTSWEEP_RAY_UNREACHED 2     /* T at the receiver is INFINITY (or NaN): no cells */
+#define TTSWEEP_RAY_INVALID 3       /* pred_dev is out of range, does not strictly decrease T, or names a cell no live
+                                       edge of the star reaches with the receiver side's time: no cells */
+
+/* Rays of nstart boxes to nrecv receivers: ray r = s*nrecv + q follows pred_dev[s] (as written by
+ * ttsweep_predecessors_device, for the same boxes) from receiver q back to a SOURCE or SEED cell.  Every hop
+ * p -> c is checked against the box (0 <= p < nx*ny*nz, T[p] < T[c], a live edge whose candidate is T[c]),
+ * so a wrong pred buffer ends a ray as TTSWEEP_RAY_INVALID and never makes a walk run on.
+ *   offsets   : host, nstart*nrecv + 1 entries: the exclusive prefix sums of the path cells (offsets[0] = 0);
+ *               ray r's cells are [offsets[r], offsets[r+1]) of cells_dev
+ *   status    : host, nstart*nrecv entries (TTSWEEP_RAY_*), may be NULL
+ *   t_recv    : host, nstart*nrecv entries, T at the receiver, may be NULL
+ *   cells_dev : device, int32 FLOATBOX indices, the path source -> receiver (hops + 1 cells)
+ *   hop_d_dev : device, float, aligned with cells_dev: the star length d of the hop from cell i to cell i+1
+ *               of the path (of duplicate entries the smallest d whose candidate is the later cell's time);
+ *               the last cell of every ray holds 0
+ * cells_dev and hop_d_dev are written only when both are non-NULL and capacity >= the total, so a caller
+ * counts first (NULL buffers), allocates, then calls again.  Replaying the hops from T[path[0]],
+ * t = fl(delay(hop_d[h], v[path[h]] + v[path[h+1]]) + t), ends at exactly t_recv for every OK and SEED ray.
+ * Returns the total number of path cells (>= 0), < 0 on error (the checks of ttsweep_predecessors_device, a
+ * receiver outside the grid, nrecv < 0, offsets NULL). */
+long long ttsweep_trace_rays_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                    const float *const *tt_dev, const int *const *pred_dev,
+                                    int nrecv, const ttsweep_start *receivers,
+                                    long long *offsets, int *status, float *t_recv,
+                                    int *cells_dev, float *hop_d_dev, long long capacity);
+
 /* Multi-GPU form of ttsweep_solve for a host program: the start points are
  * independent (serial_new/...:158-162; mpi/backup.c:351-363 runs one start per
  * rank), so the starts are dealt over the devices, longest first by estimated cost

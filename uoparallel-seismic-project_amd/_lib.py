@@ -68,6 +68,10 @@ SYMBOLS = [
     ("ttsweep_get_stats", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ttsweep_validate_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    ("ttsweep_predecessors_device", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ttsweep_trace_rays_device", C.c_longlong, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_longlong]),
     ("ttsweep_solve_multi", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     ("ttsweep_solve_multi_changed", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -89,6 +93,8 @@ OPT_ASYNC_HANDOFF = 22
 OPT_ASYNC_WAVES = 23
 OPT_TILE_ORDER = 24
 KERNEL_AUTO, KERNEL_CELL, KERNEL_STRIP, KERNEL_TILE = 0, 1, 2, 3
+PRED_SOURCE, PRED_SEED, PRED_UNREACHED = -1, -2, -3
+RAY_OK, RAY_SEED, RAY_UNREACHED, RAY_INVALID = 0, 1, 2, 3
 
 
 def build(verbose: bool = False) -> str:

@@ -224,6 +224,7 @@ void ttsweep_destroy(ttsweep_ctx *ctx)
     if (ctx->h_tile_dmin) (void)hipHostFree(ctx->h_tile_dmin);
     (void)hipFree(ctx->d_vface);
     (void)hipFree(ctx->d_tface);
+    (void)hipFree(ctx->d_rays);
     if (ctx->h_work) (void)hipHostFree(ctx->h_work);
     if (ctx->h_starts) (void)hipHostFree(ctx->h_starts);
     if (ctx->h_active) (void)hipHostFree(ctx->h_active);

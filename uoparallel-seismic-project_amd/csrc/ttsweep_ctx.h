@@ -190,6 +190,11 @@ struct ttsweep_ctx {
     std::vector<ttsweep_fs> fs_copy;        // the caller's star entries [0, starstop)
     int starstart = 0, starstop = 0;
 
+    // rays (ttsweep_rays.cpp): one device buffer for what a ray call needs besides the caller's arrays - the
+    // star's ray entries, the box records, receivers and per-ray counters (grown on demand)
+    char *d_rays = nullptr;
+    size_t rays_cap = 0;
+
     // options
     bool timing = false;
     long long max_sweeps = 100000;

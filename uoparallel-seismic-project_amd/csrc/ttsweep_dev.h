@@ -52,6 +52,22 @@ struct FwdEntry {
     float d;
 };
 
+// EXACT: the reference's own rounding of a delay - the product d (v[c] + v[o]) rounded, THEN halved
+// (serial_new/sweep-tt-multistart.c:216) - for velocity volumes with values so small that the product can be a
+// denormal number, where d / 2 times the sum rounds differently; so large that the product overflows while
+// d / 2 times the sum does not (the reference's delay is then INFINITY); and for stars with a length d whose
+// half is not a float (a subnormal d with an odd last bit): hence d itself, not h + h.
+template <bool EXACT>
+__device__ __forceinline__ float edge_delay(float h, float d, float sum)
+{
+    if (EXACT) {
+        float p = d * sum;
+        asm volatile("" : "+v"(p));     // (the product is rounded before it is halved)
+        return p * 0.5f;
+    }
+    return h * sum;
+}
+
 // Per-start device record.
 struct StartDesc {
     float *T;               // padded travel-time volume of this start

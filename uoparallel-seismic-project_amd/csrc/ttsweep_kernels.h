@@ -131,6 +131,42 @@ void column_order_sequence(int which, const int (&n)[3], const int (&at)[3], uns
 // the whole solve: the wavefronts of `nblocks` resident workgroups claim columns until every start is at rest
 hipError_t launch_column_solve(const ColumnSolve &P, int nblocks, hipStream_t st);
 
+// ---- rays (ttsweep_rays.hip): predecessors and shortest-path rays of converged boxes ----
+// One pull entry of the ray kernels, in the caller's axes: neighbour o = c + (di, dj, dk) of cell c, at
+// flat FLOATBOX index c + udelta when it is inside the grid; its velocity vdelta after the cell's own in the
+// padded volume (RayGeom).  Entries whose offset does not fit the grid are left out; the rest are sorted by (di, dj, dk, d).
+struct RayEntry {
+    int di, dj, dk, flags;  // flags: PULL_FWD / PULL_REV
+    int udelta;
+    float h, d;
+    int pad_;
+    long long vdelta;
+};
+// box s of a ray call: travel times and predecessors in the caller's FLOATBOX layout, its start cell
+struct RayBox {
+    const float *T;
+    int *pred;
+    int sflat;
+    int pad_;
+};
+// the grid in the caller's axes and where its cells lie in the padded velocity volume:
+// cell (x, y, z) at vbase + x * vs[0] + y * vs[1] + z * vs[2]
+struct RayGeom {
+    int n[3];
+    int pad_;
+    long long vbase, vs[3];
+};
+// pred[s][c] for every cell of every box (TTSWEEP_PRED_* or the smallest flat index of a predecessor)
+hipError_t launch_predecessors(const RayGeom &G, const float *v, const RayBox *boxes, int nstart,
+                               const RayEntry *entries, int nentries, bool exact, hipStream_t st);
+// fill = false: count[r], status[r], t_recv[r] of every ray r = s * nrecv + q; fill = true: also the cells and
+// hop lengths of the OK / SEED rays at [offsets[r], offsets[r + 1]) of cells / hop_d (written backwards, so a
+// path reads source -> receiver; hop_d[offsets[r + 1] - 1] = 0)
+hipError_t launch_trace_rays(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
+                             int nrecv, const RayEntry *entries, int nentries, bool exact, int *count, int *status,
+                             float *t_recv, const long long *offsets, int *cells, float *hop_d, bool fill,
+                             hipStream_t st);
+
 #ifdef TTSWEEP_TILE_PROFILE
 void tile_prof_dump();   // prints and clears the phase counters of tile_sweep_kernel
 #endif

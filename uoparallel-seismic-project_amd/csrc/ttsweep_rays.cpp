@@ -1,0 +1,197 @@
+// ttsweep_rays.cpp - the ray calls of include/ttsweep.h: ttsweep_predecessors_device and
+// ttsweep_trace_rays_device (kernels: ttsweep_rays.hip).  Argument checks, the star's ray entries, the
+// host-side scan of the per-ray cell counts.  Nothing here touches the solve's state: the boxes the
+// confirming-pass shortcut of ttsweep_solve remembers, its pools and its options stay as they are.
+#include "ttsweep_ctx.h"
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <vector>
+
+using namespace ttsweep;
+
+namespace {
+
+size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
+
+bool inside(const ttsweep_ctx *ctx, const ttsweep_start &p)
+{
+    return p.i >= 0 && p.i < ctx->nx && p.j >= 0 && p.j < ctx->ny && p.k >= 0 && p.k < ctx->nz;
+}
+
+int flat(const ttsweep_ctx *ctx, const ttsweep_start &p) { return (p.i * ctx->ny + p.j) * ctx->nz + p.k; }
+
+// what both calls check before any device work
+int check_boxes(const ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float *const *tt_dev,
+                const void *const *pred_dev, const char *what)
+{
+    if (!ctx || nstart < 0 || (nstart > 0 && (!starts || !tt_dev || !pred_dev)))
+        return set_error("%s: null or bad argument", what);
+    if ((long long)ctx->nx * ctx->ny * ctx->nz > INT_MAX)
+        return set_error("%s: %d x %d x %d cells do not fit int32 indices", what, ctx->nx, ctx->ny, ctx->nz);
+    if (!ctx->have_v) return set_error("%s: velocity not set", what);
+    for (int s = 0; s < nstart; s++) {
+        if (!tt_dev[s] || !pred_dev[s]) return set_error("%s: null box pointer %d", what, s);
+        if (!inside(ctx, starts[s]))
+            return set_error("%s: start %d (%d, %d, %d) outside the grid", what, s, starts[s].i, starts[s].j,
+                             starts[s].k);
+    }
+    return 0;
+}
+
+// the grid in the caller's axes over the padded velocity volume of the current layout
+RayGeom ray_geom(const ttsweep_ctx *ctx)
+{
+    const DevLayout &L = ctx->L;
+    RayGeom G{};
+    G.n[0] = ctx->nx; G.n[1] = ctx->ny; G.n[2] = ctx->nz;
+    const long long stride[3] = {L.s0, L.s1, 1};
+    for (int d = 0; d < 3; d++) G.vs[L.perm[d]] = stride[d];
+    G.vbase = dev_index(L, 0, 0, 0);
+    return G;
+}
+
+// the pull star as ray entries: offsets that fit the grid, sorted by (di, dj, dk, d)
+std::vector<RayEntry> ray_entries(const ttsweep_ctx *ctx, const RayGeom &G)
+{
+    std::vector<RayEntry> out;
+    for (size_t e = 0; e < ctx->pull.size(); e++) {
+        const ttsweep_pull_entry &p = ctx->pull[e];
+        if (std::abs(p.di) >= ctx->nx || std::abs(p.dj) >= ctx->ny || std::abs(p.dk) >= ctx->nz) continue;
+        RayEntry r{};
+        r.di = p.di; r.dj = p.dj; r.dk = p.dk;
+        r.flags = p.flags;
+        r.udelta = (int)(((long long)p.di * ctx->ny + p.dj) * ctx->nz + p.dk);
+        r.h = p.h;
+        r.d = ctx->pull_d[e];
+        r.vdelta = p.di * G.vs[0] + p.dj * G.vs[1] + p.dk * G.vs[2];
+        out.push_back(r);
+    }
+    std::sort(out.begin(), out.end(), [](const RayEntry &a, const RayEntry &b) {
+        if (a.di != b.di) return a.di < b.di;
+        if (a.dj != b.dj) return a.dj < b.dj;
+        if (a.dk != b.dk) return a.dk < b.dk;
+        return a.d < b.d;
+    });
+    return out;
+}
+
+// ctx->d_rays holds at least `bytes`
+int ensure_ray_buffer(ttsweep_ctx *ctx, size_t bytes)
+{
+    if (bytes <= ctx->rays_cap) return 0;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipFree(ctx->d_rays));
+    ctx->d_rays = nullptr;
+    ctx->rays_cap = 0;
+    HIPCHK(hipMalloc((void **)&ctx->d_rays, bytes));
+    ctx->rays_cap = bytes;
+    return 0;
+}
+
+// entries and box records on the device, at the front of ctx->d_rays (extra: bytes the caller needs behind them)
+struct RayStage {
+    RayGeom G;
+    std::vector<RayEntry> ent;
+    std::vector<RayBox> boxes;
+    RayEntry *d_ent = nullptr;
+    RayBox *d_boxes = nullptr;
+    char *rest = nullptr;
+};
+
+int stage(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float *const *tt_dev,
+          int *const *pred_dev, size_t extra, RayStage &S)
+{
+    S.G = ray_geom(ctx);
+    S.ent = ray_entries(ctx, S.G);
+    S.boxes.resize(nstart);
+    for (int s = 0; s < nstart; s++) S.boxes[s] = RayBox{tt_dev[s], pred_dev[s], flat(ctx, starts[s]), 0};
+    const size_t be = align_up(std::max<size_t>(S.ent.size(), 1) * sizeof(RayEntry));
+    const size_t bb = align_up(std::max(nstart, 1) * sizeof(RayBox));
+    if (ensure_ray_buffer(ctx, be + bb + extra)) return -1;
+    S.d_ent = (RayEntry *)ctx->d_rays;
+    S.d_boxes = (RayBox *)(ctx->d_rays + be);
+    S.rest = ctx->d_rays + be + bb;
+    if (!S.ent.empty())
+        HIPCHK(hipMemcpyAsync(S.d_ent, S.ent.data(), S.ent.size() * sizeof(RayEntry), hipMemcpyHostToDevice,
+                              ctx->stream));
+    if (nstart)
+        HIPCHK(hipMemcpyAsync(S.d_boxes, S.boxes.data(), nstart * sizeof(RayBox), hipMemcpyHostToDevice,
+                              ctx->stream));
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int ttsweep_predecessors_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                const float *const *tt_dev, int *const *pred_dev)
+{
+    if (check_boxes(ctx, nstart, starts, tt_dev, (const void *const *)pred_dev, "ttsweep_predecessors_device"))
+        return -1;
+    if (nstart == 0) return 0;
+    if (ctx_bind(ctx)) return -1;
+    RayStage S;
+    if (stage(ctx, nstart, starts, tt_dev, pred_dev, 0, S)) return -1;
+    HIPCHK(launch_predecessors(S.G, ctx->d_v, S.d_boxes, nstart, S.d_ent, (int)S.ent.size(), ctx->exact_half,
+                               ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // (also keeps S's host vectors alive past the copies)
+    return 0;
+}
+
+long long ttsweep_trace_rays_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                    const float *const *tt_dev, const int *const *pred_dev,
+                                    int nrecv, const ttsweep_start *receivers,
+                                    long long *offsets, int *status, float *t_recv,
+                                    int *cells_dev, float *hop_d_dev, long long capacity)
+{
+    const char *what = "ttsweep_trace_rays_device";
+    if (check_boxes(ctx, nstart, starts, tt_dev, (const void *const *)pred_dev, what)) return -1;
+    if (nrecv < 0 || (nrecv > 0 && !receivers) || !offsets) return set_error("%s: null or bad argument", what);
+    std::vector<int> recv(nrecv);
+    for (int q = 0; q < nrecv; q++) {
+        if (!inside(ctx, receivers[q]))
+            return set_error("%s: receiver %d (%d, %d, %d) outside the grid", what, q, receivers[q].i,
+                             receivers[q].j, receivers[q].k);
+        recv[q] = flat(ctx, receivers[q]);
+    }
+    const long long nrays = (long long)nstart * nrecv;
+    offsets[0] = 0;
+    if (nrays == 0) return 0;
+    if (ctx_bind(ctx)) return -1;
+    const size_t br = align_up(nrecv * sizeof(int)), bn = align_up(nrays * sizeof(int));
+    const size_t bo = align_up((nrays + 1) * sizeof(long long));
+    RayStage S;
+    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, br + 3 * bn + bo, S)) return -1;
+    int *d_recv = (int *)S.rest;
+    int *d_count = (int *)(S.rest + br);
+    int *d_status = (int *)(S.rest + br + bn);
+    float *d_trecv = (float *)(S.rest + br + 2 * bn);
+    long long *d_offsets = (long long *)(S.rest + br + 3 * bn);
+    HIPCHK(hipMemcpyAsync(d_recv, recv.data(), nrecv * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    const int nent = (int)S.ent.size();
+    HIPCHK(launch_trace_rays(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, nent, ctx->exact_half,
+                             d_count, d_status, d_trecv, nullptr, nullptr, nullptr, false, ctx->stream));
+    std::vector<int> count(nrays);
+    HIPCHK(hipMemcpyAsync(count.data(), d_count, nrays * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d_status, nrays * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (t_recv) HIPCHK(hipMemcpyAsync(t_recv, d_trecv, nrays * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    long long total = 0;
+    for (long long r = 0; r < nrays; r++) {
+        total += count[r];
+        offsets[r + 1] = total;
+    }
+    if (cells_dev && hop_d_dev && capacity >= total && total > 0) {
+        HIPCHK(hipMemcpyAsync(d_offsets, offsets, (nrays + 1) * sizeof(long long), hipMemcpyHostToDevice,
+                              ctx->stream));
+        HIPCHK(launch_trace_rays(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, nent, ctx->exact_half,
+                                 d_count, d_status, d_trecv, d_offsets, cells_dev, hop_d_dev, true, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    return total;
+}
+
+} // extern "C"

@@ -8,6 +8,7 @@ if the library or a HIP device is missing every call raises.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -122,11 +123,9 @@ class TravelTimeSolver:
     # -- the hot path -------------------------------------------------------
     @staticmethod
     def _starts_array(starts):
-        starts = np.asarray(starts, dtype=np.int32).reshape(-1, 3)
-        arr = (Start * len(starts))()
-        for s, (i, j, k) in enumerate(starts):
-            arr[s] = Start(int(i), int(j), int(k))
-        return arr
+        # one copy of the (n, 3) int32 rows: struct START is three packed ints (receiver lists are long)
+        starts = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1, 3))
+        return (Start * len(starts)).from_buffer_copy(starts.tobytes())
 
     def solve(self, starts, tt_boxes) -> int:
         """In-place solve of host boxes (numpy float32 arrays, one per start).
@@ -174,10 +173,108 @@ class TravelTimeSolver:
                                                C.byref(b), C.byref(c)), "ttsweep_validate_device")
         return a.value, b.value, c.value
 
+    # -- rays ---------------------------------------------------------------
+    def _box_pointers(self, t, n):
+        ptrs = (C.c_void_p * max(n, 1))()
+        for s in range(n):
+            ptrs[s] = t.data_ptr() + s * t.stride(0) * t.element_size()
+        return ptrs
+
+    def predecessors(self, starts, tt):
+        """ttsweep_predecessors_device: for every cell of every box of tt (torch float32 [nstart,nx,ny,nz]
+        on this solver's device) the smallest FLOATBOX index of a neighbour whose candidate is its travel
+        time, or PRED_SOURCE / PRED_SEED / PRED_UNREACHED.  Returns a torch.int32 tensor of tt's shape on
+        the same device."""
+        import torch
+        arr = self._starts_array(starts)
+        n = len(arr)
+        self._require_device_tensor(tt, (n,) + self.shape, "travel-time boxes")
+        pred = torch.empty(tt.shape, dtype=torch.int32, device=tt.device)
+        torch.cuda.current_stream(tt.device).synchronize()
+        _check(self._L.ttsweep_predecessors_device(self._ctx, n, arr, self._box_pointers(tt, n),
+                                                   self._box_pointers(pred, n)), "ttsweep_predecessors_device")
+        return pred
+
+    def trace_rays(self, starts, tt, receivers, pred=None) -> "Rays":
+        """ttsweep_trace_rays_device: the ray from every start of tt to every receiver ((nrecv, 3) cells),
+        ray r = s * nrecv + q.  pred: the result of predecessors() for these boxes (computed when None).
+        Two calls of the C ABI: one counts the path cells, the second fills the paths."""
+        import torch
+        arr = self._starts_array(starts)
+        n = len(arr)
+        self._require_device_tensor(tt, (n,) + self.shape, "travel-time boxes")
+        if pred is None:
+            pred = self.predecessors(starts, tt)
+        _require(isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_contiguous()
+                 and tuple(pred.shape) == tuple(tt.shape) and pred.device == tt.device,
+                 "pred: contiguous int32 tensor of the boxes' shape on their device")
+        recv = self._starts_array(receivers)
+        nrays = n * len(recv)
+        offsets = torch.zeros(nrays + 1, dtype=torch.int64)
+        status = torch.empty(nrays, dtype=torch.int32)
+        t_recv = torch.empty(nrays, dtype=torch.float32)
+        tptr, pptr = self._box_pointers(tt, n), self._box_pointers(pred, n)
+        torch.cuda.current_stream(tt.device).synchronize()
+
+        def call(cells, hop_d, cap):
+            return _check(self._L.ttsweep_trace_rays_device(
+                self._ctx, n, arr, tptr, pptr, len(recv), recv, offsets.data_ptr(), status.data_ptr(),
+                t_recv.data_ptr(), cells, hop_d, cap), "ttsweep_trace_rays_device")
+
+        total = call(None, None, 0)
+        cells = torch.empty(total, dtype=torch.int32, device=tt.device)
+        hop_d = torch.empty(total, dtype=torch.float32, device=tt.device)
+        if total:
+            _require(call(cells.data_ptr(), hop_d.data_ptr(), total) == total, "ray count changed between calls")
+        return Rays(offsets, cells, hop_d, status, t_recv)
+
     def stats(self) -> dict:
         st = Stats()
         _check(self._L.ttsweep_get_stats(self._ctx, C.byref(st)), "ttsweep_get_stats")
         return {name: getattr(st, name) for name, _ in Stats._fields_}
+
+
+@dataclass
+class Rays:
+    """Rays of TravelTimeSolver.trace_rays; ray r = s * nrecv + q (start s, receiver q).
+      offsets [nrays + 1] int64 (host): ray r's cells are cells[offsets[r]:offsets[r + 1]]
+      cells   int32 (device): FLOATBOX indices of the path, source -> receiver
+      hop_d   float32 (device), aligned with cells: star length of the hop to the next cell, 0 at a ray's last cell
+      status  [nrays] int32 (host): RAY_OK / RAY_SEED / RAY_UNREACHED / RAY_INVALID
+      t_recv  [nrays] float32 (host): the travel time at the receiver"""
+    offsets: "object"
+    cells: "object"
+    hop_d: "object"
+    status: "object"
+    t_recv: "object"
+
+    def __len__(self):
+        return len(self.status)
+
+
+def rays_to_frechet(rays: Rays, v_shape, dtype=None):
+    """Frechet (sensitivity) matrix of the discrete rays: a torch.sparse_coo_tensor [nrays, nx*ny*nz] on the
+    rays' device in which every hop of length d between cells a and b adds d / 2 at (ray, a) and at (ray, b):
+    the delay d (v[a] + v[b]) / 2 is linear in v, so G @ v is the sum of a ray's delays (t_recv for an OK ray,
+    t_recv - T[path[0]] for a SEED ray) and G is dt/dv of the path.  dtype: default torch.float64."""
+    import torch
+    dtype = torch.float64 if dtype is None else dtype
+    ncells = int(np.prod([int(n) for n in v_shape]))
+    dev = rays.cells.device
+    offsets = rays.offsets.to(dev)
+    nrays = len(offsets) - 1
+    counts = offsets[1:] - offsets[:-1]
+    row = torch.repeat_interleave(torch.arange(nrays, device=dev), counts)
+    half = rays.hop_d.to(dtype) / 2
+    cells = rays.cells.to(torch.int64)
+    # hop g -> g + 1 for every position g but a ray's last
+    last = torch.zeros(len(cells), dtype=torch.bool, device=dev)
+    last[offsets[1:][counts > 0] - 1] = True
+    g = torch.nonzero(~last).flatten()
+    rows = torch.cat([row[g], row[g]])
+    cols = torch.cat([cells[g], cells[g + 1]])
+    vals = torch.cat([half[g], half[g]])
+    return torch.sparse_coo_tensor(torch.stack([rows, cols]), vals, (nrays, ncells)).coalesce()
 
 
 def solve_multi(devices, v: np.ndarray, fs: np.ndarray, starts, tt_boxes, starstart: int = 0,
