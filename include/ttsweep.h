@@ -344,6 +344,44 @@ long long ttsweep_trace_rays_device(ttsweep_ctx *ctx, int nstart, const ttsweep_
                                     long long *offsets, int *status, float *t_recv,
                                     int *cells_dev, float *hop_d_dev, long long capacity);
 
+/* ---- rays: the Frechet operators G m and G^T w without stored paths ---- */
+/* G [nstart*nrecv, nx*ny*nz] is the Frechet matrix of the rays of ttsweep_trace_rays_device for the same
+ * arguments: every hop of length d (hop_d) between cells a and b of an OK or SEED ray r adds d/2 at (r, a) and
+ * at (r, b); UNREACHED and INVALID rays have an empty row.  These calls walk the rays as
+ * ttsweep_trace_rays_device does (the same checks per hop, the same statuses, the same hop_d choice) and read
+ * or scatter along the walk instead of storing it: the memory they need is the boxes, pred and their outputs.
+ * Same arguments and checks as ttsweep_trace_rays_device; also refused: nstart*nrecv > INT32_MAX.  Refusals
+ * happen before any device work, except that of a NaN or infinite weight, which is found before g is touched.
+ * They change no box and no state of the context.  Both return 0, or < 0 with ttsweep_last_error set. */
+#define TTSWEEP_HAS_RAY_OPERATORS 1 /* the two calls below exist (TTSWEEP_ABI_VERSION stays 6) */
+
+/* y = G m.  m_dev: device, double, FLOATBOX layout.  y_dev: device, double, nstart*nrecv entries.  Per ray,
+ * in walk order (receiver -> source), from y = 0.0: y = y + (0.5 * (double)d) * (m[c] + m[p]) for every hop
+ * p -> c, rounded step by step (no contraction); 0 for an UNREACHED or INVALID ray.
+ *   status : host, nstart*nrecv entries (TTSWEEP_RAY_*), may be NULL */
+int ttsweep_ray_forward_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                               const float *const *tt_dev, const int *const *pred_dev,
+                               int nrecv, const ttsweep_start *receivers,
+                               const double *m_dev, double *y_dev, int *status);
+
+/* g = G^T w and hit counts, deterministic: bit-identical from call to call, whatever the scheduling.
+ *   w_dev    : device, double, nstart*nrecv entries; NaN or infinite weights are refused
+ *   g_dev    : device, double, FLOATBOX layout, written (w_dev and g_dev both NULL: hit counts only)
+ *   hits_dev : device, int32, FLOATBOX layout: the number of OK or SEED rays whose path holds the cell; may be NULL
+ *   scale    : host, S below, may be NULL
+ * g is summed in int64 fixed point, with g_dev as the accumulator: E_w = the largest frexp exponent of the
+ * nonzero weights, E_d = the frexp exponent of the largest d among the star's ray entries (offsets that fit the
+ * grid), K = ceil(log2(nstart*nrecv)) (0 for one ray), S = 61 - E_w - E_d - K.  The visit of cell x by ray r
+ * adds llrint(ldexp(w[r] * (0.5 * ((double)d_in + (double)d_out)), S)), d_in and d_out the lengths of the
+ * path's hops into and out of x (0 where there is none); then g[x] = ldexp((double)acc[x], -S).  No sum can
+ * overflow (a visit adds less than 2^(61-K), a ray visits a cell at most once: |acc[x]| < 2^61); each visit is
+ * rounded by at most 2^-S / 2, so g[x] is within 2^-S * hits[x] / 2 of the sum of the double terms, plus the
+ * last rounding to double.  Every weight zero: g = 0 and S = 0. */
+int ttsweep_ray_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                               const float *const *tt_dev, const int *const *pred_dev,
+                               int nrecv, const ttsweep_start *receivers,
+                               const double *w_dev, double *g_dev, int *hits_dev, int *scale);
+
 /* Multi-GPU form of ttsweep_solve for a host program: the start points are
  * independent (serial_new/...:158-162; mpi/backup.c:351-363 runs one start per
  * rank), so the starts are dealt over the devices, longest first by estimated cost

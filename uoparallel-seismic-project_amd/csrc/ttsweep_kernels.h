@@ -167,6 +167,18 @@ hipError_t launch_trace_rays(const RayGeom &G, const float *v, const RayBox *box
                              float *t_recv, const long long *offsets, int *cells, float *hop_d, bool fill,
                              hipStream_t st);
 
+// the Frechet operators of the rays (status[r] of every ray; acc: the caller's g read as int64, zeroed first)
+hipError_t launch_ray_forward(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
+                              int nrecv, const RayEntry *entries, int nentries, bool exact, const double *m,
+                              double *y, int *status, hipStream_t st);
+// out[0] = max (frexp exponent + 2048) of the nonzero w (0: none), out[1] = 1 if a w is NaN or infinite; zeroed first
+hipError_t launch_ray_weight_scan(const double *w, int n, int *out, hipStream_t st);
+hipError_t launch_ray_adjoint(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
+                              int nrecv, const RayEntry *entries, int nentries, bool exact, const double *w, int S,
+                              long long *acc, int *hits, hipStream_t st);
+// g[x] = ldexp((double)acc[x], -S) in place
+hipError_t launch_ray_fixed_to_double(long long *g, long long n, int S, hipStream_t st);
+
 #ifdef TTSWEEP_TILE_PROFILE
 void tile_prof_dump();   // prints and clears the phase counters of tile_sweep_kernel
 #endif

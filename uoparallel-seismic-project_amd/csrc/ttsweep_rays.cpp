@@ -1,11 +1,13 @@
-// ttsweep_rays.cpp - the ray calls of include/ttsweep.h: ttsweep_predecessors_device and
-// ttsweep_trace_rays_device (kernels: ttsweep_rays.hip).  Argument checks, the star's ray entries, the
+// ttsweep_rays.cpp - the ray calls of include/ttsweep.h: ttsweep_predecessors_device,
+// ttsweep_trace_rays_device and the Frechet operators ttsweep_ray_forward_device / ttsweep_ray_adjoint_device
+// (kernels: ttsweep_rays.hip).  Argument checks, the star's ray entries, the
 // host-side scan of the per-ray cell counts.  Nothing here touches the solve's state: the boxes the
 // confirming-pass shortcut of ttsweep_solve remembers, its pools and its options stay as they are.
 #include "ttsweep_ctx.h"
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -38,6 +40,33 @@ int check_boxes(const ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
                              starts[s].k);
     }
     return 0;
+}
+
+// the receivers as FLOATBOX indices; each must lie inside the grid
+int flat_receivers(const ttsweep_ctx *ctx, int nrecv, const ttsweep_start *receivers, const char *what,
+                   std::vector<int> &recv)
+{
+    recv.resize(nrecv);
+    for (int q = 0; q < nrecv; q++) {
+        if (!inside(ctx, receivers[q]))
+            return set_error("%s: receiver %d (%d, %d, %d) outside the grid", what, q, receivers[q].i,
+                             receivers[q].j, receivers[q].k);
+        recv[q] = flat(ctx, receivers[q]);
+    }
+    return 0;
+}
+
+// the checks of the two operator calls before any device work: the ray counts (one int32 index per ray), the
+// boxes, the receivers
+int check_operator(const ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float *const *tt_dev,
+                   const int *const *pred_dev, int nrecv, const ttsweep_start *receivers, const char *what,
+                   std::vector<int> &recv)
+{
+    if (nstart < 0 || nrecv < 0 || (nrecv > 0 && !receivers)) return set_error("%s: null or bad argument", what);
+    if ((long long)nstart * nrecv > INT_MAX)
+        return set_error("%s: %d starts x %d receivers do not fit int32 ray indices", what, nstart, nrecv);
+    if (check_boxes(ctx, nstart, starts, tt_dev, (const void *const *)pred_dev, what)) return -1;
+    return flat_receivers(ctx, nrecv, receivers, what, recv);
 }
 
 // the grid in the caller's axes over the padded velocity volume of the current layout
@@ -150,13 +179,8 @@ long long ttsweep_trace_rays_device(ttsweep_ctx *ctx, int nstart, const ttsweep_
     const char *what = "ttsweep_trace_rays_device";
     if (check_boxes(ctx, nstart, starts, tt_dev, (const void *const *)pred_dev, what)) return -1;
     if (nrecv < 0 || (nrecv > 0 && !receivers) || !offsets) return set_error("%s: null or bad argument", what);
-    std::vector<int> recv(nrecv);
-    for (int q = 0; q < nrecv; q++) {
-        if (!inside(ctx, receivers[q]))
-            return set_error("%s: receiver %d (%d, %d, %d) outside the grid", what, q, receivers[q].i,
-                             receivers[q].j, receivers[q].k);
-        recv[q] = flat(ctx, receivers[q]);
-    }
+    std::vector<int> recv;
+    if (flat_receivers(ctx, nrecv, receivers, what, recv)) return -1;
     const long long nrays = (long long)nstart * nrecv;
     offsets[0] = 0;
     if (nrays == 0) return 0;
@@ -192,6 +216,88 @@ long long ttsweep_trace_rays_device(ttsweep_ctx *ctx, int nstart, const ttsweep_
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     return total;
+}
+
+int ttsweep_ray_forward_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                               const float *const *tt_dev, const int *const *pred_dev,
+                               int nrecv, const ttsweep_start *receivers,
+                               const double *m_dev, double *y_dev, int *status)
+{
+    const char *what = "ttsweep_ray_forward_device";
+    std::vector<int> recv;
+    if (check_operator(ctx, nstart, starts, tt_dev, pred_dev, nrecv, receivers, what, recv)) return -1;
+    const long long nrays = (long long)nstart * nrecv;
+    if (nrays == 0) return 0;
+    if (!m_dev || !y_dev) return set_error("%s: null or bad argument", what);
+    if (ctx_bind(ctx)) return -1;
+    const size_t br = align_up(nrecv * sizeof(int)), bn = align_up(nrays * sizeof(int));
+    RayStage S;
+    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, br + bn, S)) return -1;
+    int *d_recv = (int *)S.rest;
+    int *d_status = (int *)(S.rest + br);
+    HIPCHK(hipMemcpyAsync(d_recv, recv.data(), nrecv * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(launch_ray_forward(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, (int)S.ent.size(),
+                              ctx->exact_half, m_dev, y_dev, d_status, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d_status, nrays * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int ttsweep_ray_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                               const float *const *tt_dev, const int *const *pred_dev,
+                               int nrecv, const ttsweep_start *receivers,
+                               const double *w_dev, double *g_dev, int *hits_dev, int *scale)
+{
+    const char *what = "ttsweep_ray_adjoint_device";
+    std::vector<int> recv;
+    if (check_operator(ctx, nstart, starts, tt_dev, pred_dev, nrecv, receivers, what, recv)) return -1;
+    if (!w_dev != !g_dev) return set_error("%s: w and g must both be given or both be NULL", what);
+    const long long nrays = (long long)nstart * nrecv;
+    const long long ncells = (long long)ctx->nx * ctx->ny * ctx->nz;
+    if (!g_dev && !hits_dev) {
+        if (scale) *scale = 0;
+        return 0;
+    }
+    if (ctx_bind(ctx)) return -1;
+    const size_t br = align_up(std::max(nrecv, 1) * sizeof(int));
+    RayStage S;
+    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, br + 256, S)) return -1;
+    int *d_recv = (int *)S.rest;
+    int *d_scan = (int *)(S.rest + br);
+    if (nrecv)
+        HIPCHK(hipMemcpyAsync(d_recv, recv.data(), nrecv * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    // S = 61 - E_w - E_d - K: a visit adds less than 2^(E_w + E_d + S) = 2^(61 - K) in magnitude, a ray visits a
+    // cell at most once (T strictly decreases along it) and there are at most 2^K rays, so |acc[x]| < 2^61
+    int shift = 0;
+    bool weighted = false;
+    if (w_dev && nrays > 0) {
+        int scan[2] = {0, 0};
+        HIPCHK(hipMemsetAsync(d_scan, 0, 2 * sizeof(int), ctx->stream));
+        HIPCHK(launch_ray_weight_scan(w_dev, (int)nrays, d_scan, ctx->stream));
+        HIPCHK(hipMemcpyAsync(scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (scan[1]) return set_error("%s: a weight is NaN or infinite", what);
+        if (scan[0]) {
+            float dmax = 0.0f;
+            for (const RayEntry &e : S.ent) dmax = std::max(dmax, e.d);
+            int e_d = 0;
+            std::frexp((double)dmax, &e_d);
+            int k = 0;
+            while ((1LL << k) < nrays) k++;
+            shift = 61 - (scan[0] - 2048) - e_d - k;
+            weighted = true;
+        }
+    }
+    if (g_dev) HIPCHK(hipMemsetAsync(g_dev, 0, ncells * sizeof(double), ctx->stream));
+    if (hits_dev) HIPCHK(hipMemsetAsync(hits_dev, 0, ncells * sizeof(int), ctx->stream));
+    if (weighted || hits_dev)
+        HIPCHK(launch_ray_adjoint(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, (int)S.ent.size(),
+                                  ctx->exact_half, weighted ? w_dev : nullptr, shift, (long long *)g_dev, hits_dev,
+                                  ctx->stream));
+    if (weighted) HIPCHK(launch_ray_fixed_to_double((long long *)g_dev, ncells, shift, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (scale) *scale = shift;
+    return 0;
 }
 
 } // extern "C"

@@ -232,4 +232,220 @@ hipError_t launch_trace_rays(const RayGeom &G, const float *v, const RayBox *box
     return hipGetLastError();
 }
 
+
+// ---- the Frechet operators of the rays: G m and G^T w without storing a path ----
+// G is rays_to_frechet(trace_rays(...)): every hop p -> c of length d of an OK or SEED ray adds d / 2 at
+// (ray, p) and at (ray, c).  Both kernels walk one lane per ray r = s * nrecv + q like trace_rays_kernel (the
+// same checks per hop, the same statuses, the same hop_length<EXACT> choice of d) and read or scatter along
+// the walk instead of storing it.  UNREACHED and INVALID rays contribute nothing.
+
+// The walk of trace_rays_kernel from receiver q of box B: hop(c, p, d) for every hop p -> c, in walk order
+// (receiver -> source).  Returns the ray's status; *end is the cell the walk ended at.
+template <bool EXACT, class Hop>
+__device__ __forceinline__ int ray_walk(const RayGeom &G, const float *__restrict__ v, const RayBox &B,
+                                        const RayEntry *__restrict__ entries, int nentries, int q, int *end,
+                                        Hop hop)
+{
+    const int N = G.n[0] * G.n[1] * G.n[2];
+    float tc = B.T[q];
+    int c = q;
+    *end = q;
+    if (ray_unreached(tc)) return TTSWEEP_RAY_UNREACHED;
+    for (;;) {
+        const int p = B.pred[c];
+        *end = c;
+        if (p == TTSWEEP_PRED_SOURCE) return c == B.sflat ? TTSWEEP_RAY_OK : TTSWEEP_RAY_INVALID;
+        if (p == TTSWEEP_PRED_SEED) return TTSWEEP_RAY_SEED;
+        if (p < 0 || p >= N) return TTSWEEP_RAY_INVALID;
+        const float tp = B.T[p];
+        if (!(tp < tc)) return TTSWEEP_RAY_INVALID;
+        float d = 0.0f;
+        if (!hop_length<EXACT>(G, v, entries, nentries, c, p, B.sflat, tc, tp, &d)) return TTSWEEP_RAY_INVALID;
+        hop(c, p, d);
+        c = p;
+        tc = tp;
+    }
+}
+
+// y[r] = (G m)[r]: y = y + (0.5 * (double)d) * (m[c] + m[p]) per hop p -> c in walk order from y = 0.0;
+// 0 for UNREACHED and INVALID rays.  One store per ray.
+template <bool EXACT>
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_forward_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes, int nstart,
+                   const int *__restrict__ recv, int nrecv, const RayEntry *__restrict__ entries, int nentries,
+                   const double *__restrict__ m, double *__restrict__ y, int *__restrict__ status)
+{
+    const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
+    if (r >= nstart * nrecv) return;
+    const int s = r / nrecv;
+    const RayBox B = boxes[s];
+    double acc = 0.0;
+    int end;
+    const int st = ray_walk<EXACT>(G, v, B, entries, nentries, recv[r - s * nrecv], &end,
+                                   [&](int c, int p, float d) { acc = acc + (0.5 * (double)d) * (m[c] + m[p]); });
+    y[r] = (st == TTSWEEP_RAY_OK || st == TTSWEEP_RAY_SEED) ? acc : 0.0;
+    status[r] = st;
+}
+
+// The fixed-point term of one visit: llrint(ldexp(w * (0.5 * ((double)d_in + (double)d_out)), S))
+__device__ __forceinline__ long long ray_term(double w, float d_in, float d_out, int S)
+{
+    return __builtin_llrint(__builtin_ldexp(w * (0.5 * ((double)d_in + (double)d_out)), S));
+}
+
+// acc (the caller's g, as int64) += the terms of every OK / SEED ray, hits[x] += 1 per such ray through x (hits
+// may be NULL; w NULL: hits only).  A cell's term is added once it has both its hops: at the hop out of it in
+// walk order, and at the end of the walk for the last cell.  An INVALID ray's terms are already added when its
+// walk fails: the same walk again takes them back out (integer adds: exact in any order).  Every OK ray of box
+// s ends at its start cell: those terms and hits are summed across the wave first, one atomic per wave and box.
+// Every lane of a wave reaches the wave sum (no early return).
+template <bool EXACT>
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_adjoint_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes, int nstart,
+                   const int *__restrict__ recv, int nrecv, const RayEntry *__restrict__ entries, int nentries,
+                   const double *__restrict__ w, int S, unsigned long long *__restrict__ acc,
+                   int *__restrict__ hits)
+{
+    const int nrays = nstart * nrecv;
+    const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
+    const bool lane = r < nrays;
+    const double wr = (lane && w) ? w[r] : 0.0;
+    const bool weighted = wr != 0.0;
+    int st = TTSWEEP_RAY_UNREACHED, end = -1;
+    float dlast = 0.0f;
+    if (lane && (weighted || hits)) {
+        const int s = r / nrecv;
+        const RayBox B = boxes[s];
+        const int q = recv[r - s * nrecv];
+        auto visit = [&](long long sign) {
+            float dout = 0.0f;      // the hop out of the cell in the path's direction: none at the receiver
+            return [&, sign, dout](int c, int, float d) mutable {
+                if (weighted) {
+                    const long long t = ray_term(wr, d, dout, S);
+                    if (t) atomicAdd(acc + c, (unsigned long long)(sign * t));
+                }
+                if (hits) atomicAdd(hits + c, (int)sign);
+                dout = d;
+                dlast = d;
+            };
+        };
+        st = ray_walk<EXACT>(G, v, B, entries, nentries, q, &end, visit(1));
+        if (st == TTSWEEP_RAY_INVALID) {
+            int e2;
+            ray_walk<EXACT>(G, v, B, entries, nentries, q, &e2, visit(-1));
+        }
+        if (st == TTSWEEP_RAY_SEED) {           // the last cell of a SEED ray: not shared, one atomic of its own
+            if (weighted) {
+                const long long t = ray_term(wr, 0.0f, dlast, S);
+                if (t) atomicAdd(acc + end, (unsigned long long)t);
+            }
+            if (hits) atomicAdd(hits + end, 1);
+        }
+    }
+    // the start cells of the OK rays: one wave sum per distinct cell (a wave spans one box unless nrecv < 64
+    // or it straddles a box boundary)
+    bool pend = st == TTSWEEP_RAY_OK;
+    const long long mine = (pend && weighted) ? ray_term(wr, 0.0f, dlast, S) : 0;
+    unsigned long long live = __ballot(pend);
+    while (live) {
+        const int leader = __ffsll((long long)live) - 1;
+        const int key = __shfl(end, leader);
+        const bool take = pend && end == key;
+        long long sum = take ? mine : 0;
+        int n = take ? 1 : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            sum += __shfl_xor(sum, off);
+            n += __shfl_xor(n, off);
+        }
+        if ((int)__lane_id() == leader) {
+            if (sum) atomicAdd(acc + key, (unsigned long long)sum);
+            if (hits) atomicAdd(hits + key, n);
+        }
+        pend = pend && !take;
+        live = __ballot(pend);
+    }
+}
+
+// The weights' scan: out[0] = max over nonzero w of (frexp exponent + 2048) (0: every weight is zero), out[1] =
+// 1 if any weight is NaN or infinite.  Tested on the bits (the library is built with -fno-honor-nans); integer
+// max and or: the same result whatever the order.
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_weight_scan_kernel(const double *__restrict__ w, int n, int *__restrict__ out)
+{
+    int e = 0, bad = 0;
+    for (int i = blockIdx.x * RAY_BLOCK + threadIdx.x; i < n; i += gridDim.x * RAY_BLOCK) {
+        const unsigned long long u = (unsigned long long)__double_as_longlong(w[i]) & 0x7fffffffffffffffULL;
+        if (u == 0) continue;
+        const int eb = (int)(u >> 52);
+        if (eb == 2047) bad = 1;
+        else e = max(e, 2048 + (eb ? eb - 1022 : -1010 - __clzll((long long)u)));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        e = max(e, __shfl_xor(e, off));
+        bad |= __shfl_xor(bad, off);
+    }
+    if (__lane_id() == 0) {
+        if (e) atomicMax(out, e);
+        if (bad) atomicOr(out + 1, 1);
+    }
+}
+
+// g[x] = ldexp((double)acc[x], -S), in place
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_fixed_to_double_kernel(long long *__restrict__ g, long long n, int S)
+{
+    const long long x = (long long)blockIdx.x * RAY_BLOCK + threadIdx.x;
+    if (x >= n) return;
+    const double t = __builtin_ldexp((double)g[x], -S);
+    reinterpret_cast<double *>(g)[x] = t;
+}
+
+hipError_t launch_ray_forward(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
+                              int nrecv, const RayEntry *entries, int nentries, bool exact, const double *m,
+                              double *y, int *status, hipStream_t st)
+{
+    const long long nrays = (long long)nstart * nrecv;
+    if (nrays <= 0) return hipSuccess;
+    if (nrays > 0x7fffffffLL) return hipErrorInvalidValue;
+    const unsigned nblocks = (unsigned)((nrays + RAY_BLOCK - 1) / RAY_BLOCK);
+    auto kernel = exact ? ray_forward_kernel<true> : ray_forward_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, nstart, recv, nrecv, entries,
+                       nentries, m, y, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_weight_scan(const double *w, int n, int *out, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    const int want = (n + RAY_BLOCK - 1) / RAY_BLOCK;
+    const unsigned nblocks = (unsigned)(want < 1024 ? want : 1024);
+    hipLaunchKernelGGL(ray_weight_scan_kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, w, n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_adjoint(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
+                              int nrecv, const RayEntry *entries, int nentries, bool exact, const double *w, int S,
+                              long long *acc, int *hits, hipStream_t st)
+{
+    const long long nrays = (long long)nstart * nrecv;
+    if (nrays <= 0) return hipSuccess;
+    if (nrays > 0x7fffffffLL) return hipErrorInvalidValue;
+    const unsigned nblocks = (unsigned)((nrays + RAY_BLOCK - 1) / RAY_BLOCK);
+    auto kernel = exact ? ray_adjoint_kernel<true> : ray_adjoint_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, nstart, recv, nrecv, entries,
+                       nentries, w, S, (unsigned long long *)acc, hits);
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_fixed_to_double(long long *g, long long n, int S, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    const long long nblocks = (n + RAY_BLOCK - 1) / RAY_BLOCK;
+    if (nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ray_fixed_to_double_kernel, dim3((unsigned)nblocks), dim3(RAY_BLOCK), 0, st, g, n, S);
+    return hipGetLastError();
+}
+
 } // namespace ttsweep

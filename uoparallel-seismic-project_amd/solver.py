@@ -228,6 +228,12 @@ class TravelTimeSolver:
             _require(call(cells.data_ptr(), hop_d.data_ptr(), total) == total, "ray count changed between calls")
         return Rays(offsets, cells, hop_d, status, t_recv)
 
+    def frechet_operator(self, starts, tt, receivers, pred=None) -> "FrechetOperator":
+        """The Frechet matrix G of the rays from every start of tt to every receiver, as an operator
+        (ttsweep_ray_forward_device / ttsweep_ray_adjoint_device): G m and G^T w without storing a path.
+        pred: the result of predecessors() for these boxes (computed once here when None)."""
+        return FrechetOperator(self, starts, tt, receivers, pred)
+
     def stats(self) -> dict:
         st = Stats()
         _check(self._L.ttsweep_get_stats(self._ctx, C.byref(st)), "ttsweep_get_stats")
@@ -250,6 +256,190 @@ class Rays:
 
     def __len__(self):
         return len(self.status)
+
+
+class FrechetOperator:
+    """G [nrays, nx*ny*nz] of TravelTimeSolver.trace_rays + rays_to_frechet, applied by walking the rays on the
+    device instead of storing them (TravelTimeSolver.frechet_operator).  Holds the solver, the boxes, pred and
+    the start and receiver lists as C arrays (built once); the boxes and pred must not change while it is used.
+      shape      (nrays, ncells); ray r = s * nrecv + q
+      status     [nrays] int32 (host): RAY_OK / RAY_SEED / RAY_UNREACHED / RAY_INVALID
+      t_recv     [nrays] float32 (host): the travel time at the receiver
+      last_scale S of the last rmatvec: g is summed in units of 2^-S (include/ttsweep.h)"""
+
+    def __init__(self, solver, starts, tt, receivers, pred=None):
+        import torch
+        self._sol = solver
+        self._starts = solver._starts_array(starts)
+        n = len(self._starts)
+        solver._require_device_tensor(tt, (n,) + solver.shape, "travel-time boxes")
+        if pred is None:
+            pred = solver.predecessors(starts, tt)
+        _require(isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_contiguous()
+                 and tuple(pred.shape) == tuple(tt.shape) and pred.device == tt.device,
+                 "pred: contiguous int32 tensor of the boxes' shape on their device")
+        self._recv = solver._starts_array(receivers)
+        self.tt, self.pred = tt, pred
+        self._tptr, self._pptr = solver._box_pointers(tt, n), solver._box_pointers(pred, n)
+        self._nstart, self._nrecv = n, len(self._recv)
+        self.grid = solver.shape
+        self.shape = (n * len(self._recv), int(np.prod(solver.shape)))
+        self.device = tt.device
+        self.last_scale = 0
+        self.status = torch.empty(self.shape[0], dtype=torch.int32)
+        recv = torch.from_numpy(np.frombuffer(self._recv, dtype=np.int32).reshape(-1, 3).astype(np.int64))
+        flat = ((recv[:, 0] * self.grid[1] + recv[:, 1]) * self.grid[2] + recv[:, 2]).to(tt.device)
+        self.t_recv = tt.reshape(n, -1)[:, flat].reshape(-1).cpu()
+        self._forward(torch.zeros(self.shape[1], dtype=torch.float64, device=self.device), self.status)
+
+    def _cells(self, t, what):
+        import torch
+        _require(isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == self.device,
+                 f"{what}: float64 tensor on {self.device}")
+        _require(t.numel() == self.shape[1] and tuple(t.shape) in ((self.shape[1],), self.grid),
+                 f"{what}: shape {tuple(t.shape)}, want {self.grid} or ({self.shape[1]},)")
+        return t.contiguous()
+
+    def _forward(self, m, status=None):
+        import torch
+        y = torch.empty(self.shape[0], dtype=torch.float64, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        _check(self._sol._L.ttsweep_ray_forward_device(
+            self._sol._ctx, self._nstart, self._starts, self._tptr, self._pptr, self._nrecv, self._recv,
+            m.data_ptr(), y.data_ptr(), None if status is None else status.data_ptr()),
+            "ttsweep_ray_forward_device")
+        return y
+
+    def matvec(self, m):
+        """G m: m float64 [nx,ny,nz] or [ncells] on the device; float64 [nrays]."""
+        return self._forward(self._cells(m, "m"))
+
+    def _adjoint(self, w, hits):
+        import torch
+        scale = C.c_int(0)
+        g = None
+        if w is not None:
+            _require(isinstance(w, torch.Tensor) and w.dtype == torch.float64 and w.device == self.device
+                     and tuple(w.shape) == (self.shape[0],), f"w: float64 [{self.shape[0]}] on {self.device}")
+            w = w.contiguous()
+            g = torch.empty(self.grid, dtype=torch.float64, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        _check(self._sol._L.ttsweep_ray_adjoint_device(
+            self._sol._ctx, self._nstart, self._starts, self._tptr, self._pptr, self._nrecv, self._recv,
+            None if w is None else w.data_ptr(), None if g is None else g.data_ptr(),
+            None if hits is None else hits.data_ptr(), C.byref(scale)), "ttsweep_ray_adjoint_device")
+        if w is not None:
+            self.last_scale = scale.value
+        return g
+
+    def rmatvec(self, w):
+        """G^T w: w float64 [nrays] on the device; float64 [nx,ny,nz], deterministic (int64 fixed point)."""
+        return self._adjoint(w, None)
+
+    def rmatvec_hits(self, w):
+        """(G^T w, hits) of one walk."""
+        import torch
+        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
+        return self._adjoint(w, hits), hits
+
+    def hits(self):
+        """int32 [nx,ny,nz]: the number of OK or SEED rays whose path holds each cell."""
+        import torch
+        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
+        self._adjoint(None, hits)
+        return hits
+
+
+def lsqr(A, b, damp=0.0, atol=1e-8, btol=1e-8, iter_lim=None):
+    """Paige & Saunders' LSQR for min ||A x - b||^2 + damp^2 ||x||^2, in float64 torch on b's device, for any A
+    with .shape, .matvec(x) and .rmatvec(y) (a FrechetOperator, or a matrix wrapped on the CPU).  Stops as
+    scipy.sparse.linalg.lsqr does (istop 1, 2 on btol / atol; 4, 5 at machine precision; 7 at iter_lim, default
+    2 * ncols; no condition-number limit).  Returns
+    (x [ncols], istop, itn, r1norm)."""
+    import torch
+    m, n = A.shape
+    dev = b.device
+    b = b.to(torch.float64).reshape(-1)
+    iter_lim = 2 * n if iter_lim is None else iter_lim
+    eps = float(np.finfo(np.float64).eps)
+    x = torch.zeros(n, dtype=torch.float64, device=dev)
+    u = b.clone()
+    beta = float(torch.linalg.vector_norm(u))
+    bnorm = beta
+    if beta > 0:
+        u = u / beta
+        v = A.rmatvec(u).reshape(-1)
+        alfa = float(torch.linalg.vector_norm(v))
+    else:
+        v = torch.zeros(n, dtype=torch.float64, device=dev)
+        alfa = 0.0
+    if alfa > 0:
+        v = v / alfa
+    wv = v.clone()
+    rhobar, phibar = alfa, beta
+    anorm, ddnorm, res2, xxnorm, z, cs2, sn2 = 0.0, 0.0, 0.0, 0.0, 0.0, -1.0, 0.0
+    rnorm, r1norm, arnorm = beta, beta, alfa * beta
+    itn, istop = 0, 0
+    if arnorm == 0:
+        return x, 0, 0, r1norm
+    while itn < iter_lim:
+        itn += 1
+        u = A.matvec(v).reshape(-1) - alfa * u
+        beta = float(torch.linalg.vector_norm(u))
+        if beta > 0:
+            u = u / beta
+            anorm = (anorm ** 2 + alfa ** 2 + beta ** 2 + damp ** 2) ** 0.5
+            v = A.rmatvec(u).reshape(-1) - beta * v
+            alfa = float(torch.linalg.vector_norm(v))
+            if alfa > 0:
+                v = v / alfa
+        rhobar1 = (rhobar ** 2 + damp ** 2) ** 0.5
+        cs1, sn1 = rhobar / rhobar1, damp / rhobar1
+        psi = sn1 * phibar
+        phibar = cs1 * phibar
+        rho = (rhobar1 ** 2 + beta ** 2) ** 0.5
+        cs, sn = rhobar1 / rho, beta / rho
+        theta = sn * alfa
+        rhobar = -cs * alfa
+        phi = cs * phibar
+        phibar = sn * phibar
+        tau = sn * phi
+        t1, t2 = phi / rho, -theta / rho
+        dk = wv / rho
+        x = x + t1 * wv
+        wv = v + t2 * wv
+        ddnorm += float(torch.linalg.vector_norm(dk)) ** 2
+        delta = sn2 * rho
+        gambar = -cs2 * rho
+        rhs = phi - delta * z
+        zbar = rhs / gambar
+        xnorm = (xxnorm + zbar ** 2) ** 0.5
+        gamma = (gambar ** 2 + theta ** 2) ** 0.5
+        cs2, sn2 = gambar / gamma, theta / gamma
+        z = rhs / gamma
+        xxnorm += z ** 2
+        res1 = phibar ** 2
+        res2 += psi ** 2
+        rnorm = (res1 + res2) ** 0.5
+        arnorm = alfa * abs(tau)
+        r1sq = rnorm ** 2 - damp ** 2 * xxnorm
+        r1norm = abs(r1sq) ** 0.5 * (-1 if r1sq < 0 else 1)
+        test1 = rnorm / bnorm
+        test2 = arnorm / (anorm * rnorm + eps)
+        rtol = btol + atol * anorm * xnorm / bnorm
+        if 1 + test2 <= 1:
+            istop = 5
+        if 1 + test1 / (1 + anorm * xnorm / bnorm) <= 1:
+            istop = 4
+        if test2 <= atol:
+            istop = 2
+        if test1 <= rtol:
+            istop = 1
+        if istop:
+            break
+    if not istop and itn >= iter_lim:
+        istop = 7
+    return x, istop, itn, r1norm
 
 
 def rays_to_frechet(rays: Rays, v_shape, dtype=None):
