@@ -382,6 +382,35 @@ int ttsweep_ray_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start
                                int nrecv, const ttsweep_start *receivers,
                                const double *w_dev, double *g_dev, int *hits_dev, int *scale);
 
+/* ---- locate: grid-search event location over station travel-time boxes ---- */
+/* By reciprocity, box k solved from station k as its start holds T_k[x], the travel time between the station and a
+ * candidate hypocentre x.  For each of nevent events with picks o[e][k] and weights w[e][k] (double, [nevent][nbox],
+ * device; weights_dev NULL: every weight 1.0; w = 0: station k has no pick for e) every cell x is scored in double,
+ * stations in ascending k, the stations with w[e][k] == 0 skipped in every sum, each operation rounded on its own:
+ *   W     = 0.0;  W  = W + w[e][k]                                          invW = 1.0 / W
+ *   S1    = 0.0;  S1 = S1 + w[e][k] * (o[e][k] - (double)T_k[x])            t0(x) = S1 * invW
+ *   J(x)  = 0.0;  J  = J + (w[e][k] * r) * r,   r = (o[e][k] - (double)T_k[x]) - t0(x)
+ * the weighted L2 misfit with the origin time eliminated.  x is inadmissible for e when a picked station has
+ * T_k[x] >= +INFINITY or J(x) is not below +INFINITY; then J(x) = +INFINITY.  Per event:
+ *   cell[e]   the smallest FLOATBOX index among the admissible cells of minimal J, -1 when there is none
+ *   misfit[e] J(cell[e]), +INFINITY when there is none
+ *   t0[e]     t0(cell[e]), a quiet NaN when there is none
+ * Bit-identical from call to call, whatever the launch, the batch or which events share the call.
+ *   tt_dev          : host array of nbox device pointers to float boxes (FLOATBOX layout); any float values
+ *   cell_dev, misfit_dev, t0_dev : device, nevent entries each, int32 / double / double; each may be NULL
+ *   vol_events      : host, nvol event indices in [0, nevent); vol_dev: host array of nvol device pointers to double
+ *                     volumes (FLOATBOX layout) that receive J of those events, +INFINITY where inadmissible
+ * Refused, before any output is touched: a NaN or infinite pick (also of a station without a pick); a negative,
+ * NaN or infinite weight; an event whose weights are all zero; nbox < 1, nevent < 1, nvol < 0 or > 65535, a NULL
+ * pointer where one is needed, a volume event outside [0, nevent); nbox * nevent > INT32_MAX; grids of more than
+ * INT32_MAX cells.  The boxes and the context's state are left as they are (a following ttsweep_solve of the same
+ * boxes is still answered as a confirming pass).  Returns 0, or < 0 with ttsweep_last_error set. */
+#define TTSWEEP_HAS_LOCATE 1 /* the call below exists (TTSWEEP_ABI_VERSION stays 6) */
+int ttsweep_locate_device(ttsweep_ctx *ctx, int nbox, const float *const *tt_dev,
+                          int nevent, const double *picks_dev, const double *weights_dev,
+                          int *cell_dev, double *misfit_dev, double *t0_dev,
+                          int nvol, const int *vol_events, double *const *vol_dev);
+
 /* Multi-GPU form of ttsweep_solve for a host program: the start points are
  * independent (serial_new/...:158-162; mpi/backup.c:351-363 runs one start per
  * rank), so the starts are dealt over the devices, longest first by estimated cost

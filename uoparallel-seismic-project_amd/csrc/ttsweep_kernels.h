@@ -179,6 +179,23 @@ hipError_t launch_ray_adjoint(const RayGeom &G, const float *v, const RayBox *bo
 // g[x] = ldexp((double)acc[x], -S) in place
 hipError_t launch_ray_fixed_to_double(long long *g, long long n, int S, hipStream_t st);
 
+// event location (ttsweep_locate.hip).  check: invw[e] = 1.0 / W and flag[e] (bit 0 a non-finite pick, bit 1 a
+// negative or non-finite weight, bit 2 no weight above zero) of every event; search: the per-tile partials
+// [(e - e0) * ntiles + tile] of events e0 .. e0 + ne - 1; final: cell / misfit / t0 (each may be nullptr) of those
+// events from the partials; volume: vol[v][x] = J of event vev[v]
+int locate_tile_cells();
+hipError_t launch_locate_check(int K, int nevent, const double *picks, const double *weights, double *invw, int *flag,
+                               hipStream_t st);
+hipError_t launch_locate_search(const float *const *boxes, int K, int N, const double *picks, const double *weights,
+                                const double *invw, int e0, int ne, int ntiles, unsigned long long *part_key,
+                                int *part_x, hipStream_t st);
+hipError_t launch_locate_final(const float *const *boxes, int K, const double *picks, const double *weights,
+                               const double *invw, int e0, int ne, int ntiles, const unsigned long long *part_key,
+                               const int *part_x, int *cell, double *misfit, double *t0, unsigned long long nan_bits,
+                               hipStream_t st);
+hipError_t launch_locate_volume(const float *const *boxes, int K, int N, const double *picks, const double *weights,
+                                const double *invw, const int *vev, double *const *vol, int nvol, hipStream_t st);
+
 #ifdef TTSWEEP_TILE_PROFILE
 void tile_prof_dump();   // prints and clears the phase counters of tile_sweep_kernel
 #endif

@@ -1,0 +1,343 @@
+// ttsweep_locate.hip - grid-search event location over station travel-time boxes (include/ttsweep.h, "locate").
+//
+// By reciprocity T_k[x] is the travel time between station k and a candidate hypocentre x.  For every event e
+// and cell x the weighted L2 misfit of the picks with the origin time eliminated is, in double, stations in
+// ascending k, zero weights skipped (-ffp-contract=off: every operation rounded on its own):
+//   S1 = S1 + w * (o - (double)T)        t0 = S1 * invW        J = J + (w * r) * r,  r = (o - (double)T) - t0
+// These kernels:
+//   locate_check_kernel     one lane per event: refuses non-finite picks, negative / non-finite weights and
+//                           events without a weight (flag per event, on the bits: the library is built with
+//                           -fno-honor-nans) and computes invW = 1.0 / W
+//   locate_search_kernel    one lane per cell of a tile of LOC_C * LOC_BLOCK cells, LOC_ET events per block; the
+//                           lane keeps its best (J, x) per event in LDS across its cells, then one wave
+//                           reduction per event and tile gives a per-tile partial (J bits, x)
+//   locate_final_kernel     one block per event: the smallest (J bits, x) over the tiles, then t0 at that cell
+//   locate_volume_kernel    J (+INF where inadmissible) of every cell for a list of events
+// A cell is inadmissible when a picked station has T >= +INFINITY or J is not below +INFINITY.  The first implies
+// the second in IEEE arithmetic (o - INF = -INF enters S1, so t0 is -INF or NaN and r of that station is NaN), so
+// one test on the bits of J covers both: J >= 0 always, and +INF and every NaN compare above it as unsigned
+// integers.  The argmin is the lexicographic minimum of (bits of J, x): the same whatever order the tiles, lanes
+// and waves are combined in, so results do not depend on the launch or on which events share a batch.  No float
+// atomics.  T is read through (double) of the float: exact.
+#include "ttsweep_kernels.h"
+
+#include "../../include/ttsweep.h"
+
+namespace ttsweep {
+
+constexpr int LOC_BLOCK = 256;
+constexpr int LOC_ET = 8;       // events per search block
+constexpr int LOC_C = 16;       // cells per lane per search block: a tile is LOC_C * LOC_BLOCK cells
+constexpr unsigned long long LOC_INF = 0x7ff0000000000000ULL;
+
+__device__ __forceinline__ unsigned long long dbits(double x) { return (unsigned long long)__double_as_longlong(x); }
+
+// the station k of an event with weights w (nullptr: every weight 1.0) is picked
+__device__ __forceinline__ bool loc_picked(const double *__restrict__ w, int k)
+{
+    return !w || (dbits(w[k]) << 1) != 0;
+}
+
+__device__ __forceinline__ double loc_w(const double *__restrict__ w, int k) { return w ? w[k] : 1.0; }
+
+// J and t0 of one event at the cell whose travel times are t(k), the semantics of include/ttsweep.h
+template <int KR, typename TF>
+__device__ __forceinline__ double loc_misfit(TF t, int K, const double *__restrict__ o, const double *__restrict__ w,
+                                             double invw, double &t0)
+{
+    double s1 = 0.0, J = 0.0;
+    if constexpr (KR > 0) {
+#pragma unroll
+        for (int k = 0; k < KR; k++)
+            if (k < K && loc_picked(w, k)) {
+                const double d = o[k] - t(k);
+                s1 = s1 + loc_w(w, k) * d;
+            }
+        t0 = s1 * invw;
+#pragma unroll
+        for (int k = 0; k < KR; k++)
+            if (k < K && loc_picked(w, k)) {
+                const double r = (o[k] - t(k)) - t0;
+                J = J + (loc_w(w, k) * r) * r;
+            }
+    } else {
+        for (int k = 0; k < K; k++)
+            if (loc_picked(w, k)) {
+                const double d = o[k] - t(k);
+                s1 = s1 + loc_w(w, k) * d;
+            }
+        t0 = s1 * invw;
+        for (int k = 0; k < K; k++)
+            if (loc_picked(w, k)) {
+                const double r = (o[k] - t(k)) - t0;
+                J = J + (loc_w(w, k) * r) * r;
+            }
+    }
+    return J;
+}
+
+__device__ __forceinline__ bool loc_less(unsigned long long ka, int xa, unsigned long long kb, int xb)
+{
+    return ka < kb || (ka == kb && xa < xb);
+}
+
+// the lexicographic minimum of (key, x) over the 64 lanes of the wave, in every lane
+__device__ __forceinline__ void loc_wave_min(unsigned long long &key, int &x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long k2 = __shfl_xor(key, off);
+        const int x2 = __shfl_xor(x, off);
+        if (loc_less(k2, x2, key, x)) {
+            key = k2;
+            x = x2;
+        }
+    }
+}
+
+// flag[e]: bit 0 a non-finite pick, bit 1 a negative or non-finite weight, bit 2 no weight above zero
+__global__ void __launch_bounds__(LOC_BLOCK)
+locate_check_kernel(int K, int nevent, const double *__restrict__ picks, const double *__restrict__ weights,
+                    double *__restrict__ invw, int *__restrict__ flag)
+{
+    const int e = blockIdx.x * LOC_BLOCK + threadIdx.x;
+    if (e >= nevent) return;
+    const double *o = picks + (long long)e * K;
+    const double *w = weights ? weights + (long long)e * K : nullptr;
+    int f = 0;
+    double W = 0.0;
+    for (int k = 0; k < K; k++) {
+        if (((dbits(o[k]) >> 52) & 0x7ff) == 0x7ff) f |= 1;
+        if (w) {
+            const unsigned long long u = dbits(w[k]);
+            if (((u >> 52) & 0x7ff) == 0x7ff || (u >> 63 && (u << 1) != 0)) {
+                f |= 2;
+                continue;
+            }
+        }
+        if (loc_picked(w, k)) W = W + loc_w(w, k);
+    }
+    if ((dbits(W) << 1) == 0) f |= 4;
+    invw[e] = f ? 0.0 : 1.0 / W;
+    flag[e] = f;
+}
+
+// blockIdx.x: a tile of LOC_C * LOC_BLOCK cells; blockIdx.y: LOC_ET events from e0.  Writes part_key / part_x
+// [(e - e0) * ntiles + tile] (J bits, x) of the best admissible cell of the tile, (+INF bits, INT_MAX) when none.
+template <int KR>
+__global__ void __launch_bounds__(LOC_BLOCK)
+locate_search_kernel(const float *const *__restrict__ boxes, int K, int N, const double *__restrict__ picks,
+                     const double *__restrict__ weights, const double *__restrict__ invw, int e0, int ne, int ntiles,
+                     unsigned long long *__restrict__ part_key, int *__restrict__ part_x)
+{
+    __shared__ unsigned long long s_key[LOC_ET][LOC_BLOCK];
+    __shared__ int s_x[LOC_ET][LOC_BLOCK];
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.x;
+    const int eb = blockIdx.y * LOC_ET;                 // first event of the block, relative to e0
+    const int net = min(LOC_ET, ne - eb);
+#pragma unroll
+    for (int i = 0; i < LOC_ET; i++) {
+        s_key[i][tid] = LOC_INF;
+        s_x[i][tid] = 0x7fffffff;
+    }
+    // the cell loop and the event loop are uniform (lanes past the grid compute the last cell and keep nothing), so
+    // the picks and weights are uniform loads and a zero weight is a uniform branch
+    const long long base = (long long)tile * (LOC_C * LOC_BLOCK);
+    const int nj = (int)min((long long)LOC_C, (N - base + LOC_BLOCK - 1) / LOC_BLOCK);
+    for (int j = 0; j < nj; j++) {
+        const long long xl = base + (long long)j * LOC_BLOCK + tid;
+        const bool in = xl < N;
+        const int x = in ? (int)xl : N - 1;
+        double tr[KR > 0 ? KR : 1];
+        if constexpr (KR > 0) {
+#pragma unroll
+            for (int k = 0; k < KR; k++) tr[k] = k < K ? (double)boxes[k][x] : 0.0;
+        }
+        for (int i = 0; i < net; i++) {
+            const int e = __builtin_amdgcn_readfirstlane(e0 + eb + i);
+            const double *o = picks + (long long)e * K;
+            const double *w = weights ? weights + (long long)e * K : nullptr;
+            double t0;
+            const double J = KR > 0 ? loc_misfit<KR>([&](int k) { return tr[k]; }, K, o, w, invw[e], t0)
+                                    : loc_misfit<0>([&](int k) { return (double)boxes[k][x]; }, K, o, w, invw[e], t0);
+            const unsigned long long key = dbits(J);
+            if (in && key < s_key[i][tid]) {     // cells of a lane ascend: strict keeps the smallest x
+                s_key[i][tid] = key;
+                s_x[i][tid] = x;
+            }
+        }
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int i = wave; i < net; i += LOC_BLOCK / 64) {
+        unsigned long long key = s_key[i][lane];
+        int x = s_x[i][lane];
+#pragma unroll
+        for (int q = 1; q < LOC_BLOCK / 64; q++) {
+            const unsigned long long k2 = s_key[i][lane + 64 * q];
+            const int x2 = s_x[i][lane + 64 * q];
+            if (loc_less(k2, x2, key, x)) {
+                key = k2;
+                x = x2;
+            }
+        }
+        loc_wave_min(key, x);
+        if (lane == 0) {
+            const long long p = (long long)(eb + i) * ntiles + tile;
+            part_key[p] = key;
+            part_x[p] = x;
+        }
+    }
+}
+
+// one block per event e0 + blockIdx.x: the smallest (J bits, x) over the tiles; cell, misfit and t0 (bits) of it,
+// or (-1, +INF, nan_bits) when no cell is admissible (the NaN comes from the host)
+template <int KR>
+__global__ void __launch_bounds__(LOC_BLOCK)
+locate_final_kernel(const float *const *__restrict__ boxes, int K, const double *__restrict__ picks,
+                    const double *__restrict__ weights, const double *__restrict__ invw, int e0, int ntiles,
+                    const unsigned long long *__restrict__ part_key, const int *__restrict__ part_x,
+                    int *__restrict__ cell, unsigned long long *__restrict__ misfit, unsigned long long *__restrict__ t0out,
+                    unsigned long long nan_bits)
+{
+    __shared__ unsigned long long s_key[LOC_BLOCK / 64];
+    __shared__ int s_x[LOC_BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int eo = blockIdx.x;
+    const int e = e0 + eo;
+    unsigned long long key = LOC_INF;
+    int x = 0x7fffffff;
+    for (int t = tid; t < ntiles; t += LOC_BLOCK) {
+        const long long p = (long long)eo * ntiles + t;
+        if (loc_less(part_key[p], part_x[p], key, x)) {
+            key = part_key[p];
+            x = part_x[p];
+        }
+    }
+    loc_wave_min(key, x);
+    if (lane == 0) {
+        s_key[wave] = key;
+        s_x[wave] = x;
+    }
+    __syncthreads();
+    if (tid) return;
+    key = s_key[0];
+    x = s_x[0];
+    for (int q = 1; q < LOC_BLOCK / 64; q++)
+        if (loc_less(s_key[q], s_x[q], key, x)) {
+            key = s_key[q];
+            x = s_x[q];
+        }
+    const bool found = key < LOC_INF;
+    unsigned long long tb = nan_bits;
+    if (found) {
+        const double *o = picks + (long long)e * K;
+        const double *w = weights ? weights + (long long)e * K : nullptr;
+        double t0;
+        loc_misfit<0>([&](int k) { return (double)boxes[k][x]; }, K, o, w, invw[e], t0);
+        tb = dbits(t0);
+    }
+    if (cell) cell[e] = found ? x : -1;
+    if (misfit) misfit[e] = found ? key : LOC_INF;
+    if (t0out) t0out[e] = tb;
+}
+
+// blockIdx.y: entry v of the volume list; vol[v][x] = J of event vev[v] at x, +INF where inadmissible
+template <int KR>
+__global__ void __launch_bounds__(LOC_BLOCK)
+locate_volume_kernel(const float *const *__restrict__ boxes, int K, int N, const double *__restrict__ picks,
+                     const double *__restrict__ weights, const double *__restrict__ invw, const int *__restrict__ vev,
+                     unsigned long long *const *__restrict__ vol)
+{
+    const long long xl = (long long)blockIdx.x * LOC_BLOCK + threadIdx.x;
+    if (xl >= N) return;
+    const int x = (int)xl;
+    const int e = vev[blockIdx.y];
+    const double *o = picks + (long long)e * K;
+    const double *w = weights ? weights + (long long)e * K : nullptr;
+    double t0;
+    double J;
+    if constexpr (KR > 0) {
+        double tr[KR];
+#pragma unroll
+        for (int k = 0; k < KR; k++) tr[k] = k < K ? (double)boxes[k][x] : 0.0;
+        J = loc_misfit<KR>([&](int k) { return tr[k]; }, K, o, w, invw[e], t0);
+    } else {
+        J = loc_misfit<0>([&](int k) { return (double)boxes[k][x]; }, K, o, w, invw[e], t0);
+    }
+    const unsigned long long key = dbits(J);
+    vol[blockIdx.y][x] = key < LOC_INF ? key : LOC_INF;
+}
+
+int locate_tile_cells() { return LOC_C * LOC_BLOCK; }
+
+hipError_t launch_locate_check(int K, int nevent, const double *picks, const double *weights, double *invw, int *flag,
+                               hipStream_t st)
+{
+    if (nevent <= 0) return hipSuccess;
+    hipLaunchKernelGGL(locate_check_kernel, dim3((nevent + LOC_BLOCK - 1) / LOC_BLOCK), dim3(LOC_BLOCK), 0, st, K,
+                       nevent, picks, weights, invw, flag);
+    return hipGetLastError();
+}
+
+// the register width of the stations: the smallest of 8 / 16 / 24 / 32 that holds K, 0 (read T on use) above 32
+static int loc_kr(int K) { return K <= 8 ? 8 : K <= 16 ? 16 : K <= 24 ? 24 : K <= 32 ? 32 : 0; }
+
+hipError_t launch_locate_search(const float *const *boxes, int K, int N, const double *picks, const double *weights,
+                                const double *invw, int e0, int ne, int ntiles, unsigned long long *part_key,
+                                int *part_x, hipStream_t st)
+{
+    if (ne <= 0 || ntiles <= 0) return hipSuccess;
+    const dim3 grid(ntiles, (ne + LOC_ET - 1) / LOC_ET);
+    if (grid.y > 65535) return hipErrorInvalidValue;
+    switch (loc_kr(K)) {
+    case 8: hipLaunchKernelGGL(locate_search_kernel<8>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                               invw, e0, ne, ntiles, part_key, part_x); break;
+    case 16: hipLaunchKernelGGL(locate_search_kernel<16>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                                invw, e0, ne, ntiles, part_key, part_x); break;
+    case 24: hipLaunchKernelGGL(locate_search_kernel<24>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                                invw, e0, ne, ntiles, part_key, part_x); break;
+    case 32: hipLaunchKernelGGL(locate_search_kernel<32>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                                invw, e0, ne, ntiles, part_key, part_x); break;
+    default: hipLaunchKernelGGL(locate_search_kernel<0>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                                invw, e0, ne, ntiles, part_key, part_x); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_final(const float *const *boxes, int K, const double *picks, const double *weights,
+                               const double *invw, int e0, int ne, int ntiles, const unsigned long long *part_key,
+                               const int *part_x, int *cell, double *misfit, double *t0, unsigned long long nan_bits,
+                               hipStream_t st)
+{
+    if (ne <= 0) return hipSuccess;
+    hipLaunchKernelGGL(locate_final_kernel<0>, dim3(ne), dim3(LOC_BLOCK), 0, st, boxes, K, picks, weights, invw, e0,
+                       ntiles, part_key, part_x, cell, (unsigned long long *)misfit, (unsigned long long *)t0,
+                       nan_bits);
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_volume(const float *const *boxes, int K, int N, const double *picks, const double *weights,
+                                const double *invw, const int *vev, double *const *vol, int nvol, hipStream_t st)
+{
+    if (nvol <= 0 || N <= 0) return hipSuccess;
+    const dim3 grid((N + LOC_BLOCK - 1) / LOC_BLOCK, nvol);
+    if (grid.y > 65535) return hipErrorInvalidValue;
+    auto v = (unsigned long long *const *)vol;
+    switch (loc_kr(K)) {
+    case 8: hipLaunchKernelGGL(locate_volume_kernel<8>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                               invw, vev, v); break;
+    case 16: hipLaunchKernelGGL(locate_volume_kernel<16>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                                invw, vev, v); break;
+    case 24: hipLaunchKernelGGL(locate_volume_kernel<24>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                                invw, vev, v); break;
+    case 32: hipLaunchKernelGGL(locate_volume_kernel<32>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                                invw, vev, v); break;
+    default: hipLaunchKernelGGL(locate_volume_kernel<0>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
+                                invw, vev, v); break;
+    }
+    return hipGetLastError();
+}
+
+} // namespace ttsweep

@@ -234,6 +234,51 @@ class TravelTimeSolver:
         pred: the result of predecessors() for these boxes (computed once here when None)."""
         return FrechetOperator(self, starts, tt, receivers, pred)
 
+    # -- event location -----------------------------------------------------
+    def locate(self, tt, picks, weights=None, misfit_events=None) -> "Locations":
+        """ttsweep_locate_device: grid-search location of events over station boxes (include/ttsweep.h, "locate").
+        tt: torch float32 [K,nx,ny,nz] on this solver's device, box k solved from station k.  picks, weights:
+        [E,K] float64 torch tensors on that device, or numpy arrays (copied over); weights None: every weight 1.0,
+        a zero weight: no pick.  misfit_events: event indices whose misfit volume J is returned as well."""
+        import torch
+        _require(isinstance(tt, torch.Tensor) and tt.dim() == 4, "tt: torch float32 [K, nx, ny, nz]")
+        K = int(tt.shape[0])
+        self._require_device_tensor(tt, (K,) + self.shape, "station boxes")
+        dev = tt.device
+
+        def events_by_stations(a, what):
+            if isinstance(a, np.ndarray):
+                _require(a.dtype == np.float64, f"{what}: float64")
+                a = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            _require(isinstance(a, torch.Tensor) and a.dtype == torch.float64 and a.device == dev,
+                     f"{what}: float64 tensor on {dev} or numpy array")
+            _require(a.dim() == 2 and a.shape[1] == K and a.shape[0] >= 1, f"{what}: shape {tuple(a.shape)}, want [E, {K}]")
+            return a.contiguous()
+
+        picks = events_by_stations(picks, "picks")
+        E = int(picks.shape[0])
+        if weights is not None:
+            weights = events_by_stations(weights, "weights")
+            _require(tuple(weights.shape) == (E, K), f"weights: shape {tuple(weights.shape)}, want {(E, K)}")
+        vev = [] if misfit_events is None else [int(e) for e in misfit_events]
+        _require(all(0 <= e < E for e in vev), f"misfit_events: indices in [0, {E})")
+        cell = torch.empty(E, dtype=torch.int32, device=dev)
+        misfit = torch.empty(E, dtype=torch.float64, device=dev)
+        t0 = torch.empty(E, dtype=torch.float64, device=dev)
+        vols = torch.empty((len(vev),) + self.shape, dtype=torch.float64, device=dev) if vev else None
+        varr = (C.c_int * max(len(vev), 1))(*vev)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.ttsweep_locate_device(
+            self._ctx, K, self._box_pointers(tt, K), E, picks.data_ptr(),
+            None if weights is None else weights.data_ptr(), cell.data_ptr(), misfit.data_ptr(), t0.data_ptr(),
+            len(vev), varr if vev else None, self._box_pointers(vols, len(vev)) if vev else None),
+            "ttsweep_locate_device")
+        c = cell.cpu().to(torch.int64)
+        nyz = self.shape[1] * self.shape[2]
+        xyz = torch.stack([c // nyz, (c // self.shape[2]) % self.shape[1], c % self.shape[2]], dim=1).to(torch.int32)
+        xyz[c < 0] = -1
+        return Locations(cell, xyz, misfit, t0, vols)
+
     def stats(self) -> dict:
         st = Stats()
         _check(self._L.ttsweep_get_stats(self._ctx, C.byref(st)), "ttsweep_get_stats")
@@ -256,6 +301,24 @@ class Rays:
 
     def __len__(self):
         return len(self.status)
+
+
+@dataclass
+class Locations:
+    """Events located by TravelTimeSolver.locate (include/ttsweep.h, "locate"), E events.
+      cell    [E] int32 (device): FLOATBOX index of the best cell, -1 when no cell is admissible
+      xyz     [E,3] int32 (host): the cell as (x, y, z), (-1, -1, -1) when there is none
+      misfit  [E] float64 (device): the weighted L2 misfit J at the cell, +inf when there is none
+      t0      [E] float64 (device): the origin time at the cell, NaN when there is none
+      volumes [nvol,nx,ny,nz] float64 (device) or None: J of every cell for misfit_events, +inf where inadmissible"""
+    cell: "object"
+    xyz: "object"
+    misfit: "object"
+    t0: "object"
+    volumes: "object"
+
+    def __len__(self):
+        return len(self.cell)
 
 
 class FrechetOperator:
