@@ -411,6 +411,36 @@ int ttsweep_locate_device(ttsweep_ctx *ctx, int nbox, const float *const *tt_dev
                           int *cell_dev, double *misfit_dev, double *t0_dev,
                           int nvol, const int *vol_events, double *const *vol_dev);
 
+/* ---- locate confidence: confidence regions of located events, without misfit volumes ---- */
+/* J(x), t0(x) and admissibility are exactly those of "locate" above: the same operations in the same order, so the
+ * same bits.  Per event e a reference level m[e] (normally misfit[e] of ttsweep_locate_device) and nlevel thresholds
+ * delta[e][l] (double, device, [nevent] and [nevent][nlevel], 1 <= nlevel <= 4).  For event e and level l
+ *   thr    = m[e] + delta[e][l]                          (one double addition)
+ *   R(e,l) = { x admissible for e  and  J(x) <= thr }
+ * and with the FLOATBOX index c = (x*ny + y)*nz + z, per (e, l) ([nevent][nlevel] leading dimensions, device):
+ *   count  int64      the number of cells of R                                         empty region: 0
+ *   sum    int64 [3]  sum of x, of y, of z over R                                                     0
+ *   sum2   int64 [6]  sum of xx, yy, zz, xy, xz, yz over R                                            0
+ *   lo, hi int32 [3]  the bounding box of R, inclusive                   lo = (nx, ny, nz), hi = (-1, -1, -1)
+ *   t0_lo, t0_hi double  the least and greatest t0(x) over R in IEEE totalOrder (-0 below +0)  +INFINITY, -INFINITY
+ * t0(x) is finite on every admissible cell, so both extremes are finite whenever count > 0.  m[e] = +INFINITY (an
+ * event locate found no cell for) gives the empty region at every level, by definition and before thr is formed
+ * (also for delta = +INFINITY).  delta = +INFINITY is allowed and gives every admissible cell.  m is a level, not
+ * checked to be the minimum.  Every output is an integer sum, minimum or maximum (t0 through an ordered key), so the
+ * results are identical from call to call, whatever the launch, the batch or which events share the call.  Each
+ * output may be NULL.  The call allocates nothing that grows with the grid.
+ * Refused, before any output is touched: everything ttsweep_locate_device refuses for picks and weights; a NaN or
+ * negative m[e]; a NaN or negative delta; nlevel outside 1..4; nbox < 1, nevent < 1, a NULL pointer where one is
+ * needed; nbox * nevent > INT32_MAX; grids of more than INT32_MAX cells or with ncells * max(nx, ny, nz)^2 >= 2^63
+ * (the second moments could overflow).  The checks are on the bits (-0.0 is zero).  The boxes and the context's
+ * state are left as they are.  Returns 0, or < 0 with ttsweep_last_error set. */
+#define TTSWEEP_HAS_LOCATE_CONFIDENCE 1 /* the call below exists (TTSWEEP_ABI_VERSION stays 6) */
+int ttsweep_locate_confidence_device(ttsweep_ctx *ctx, int nbox, const float *const *tt_dev,
+                                     int nevent, const double *picks_dev, const double *weights_dev,
+                                     const double *misfit_dev, int nlevel, const double *delta_dev,
+                                     long long *count_dev, long long *sum_dev, long long *sum2_dev,
+                                     int *lo_dev, int *hi_dev, double *t0_lo_dev, double *t0_hi_dev);
+
 /* Multi-GPU form of ttsweep_solve for a host program: the start points are
  * independent (serial_new/...:158-162; mpi/backup.c:351-363 runs one start per
  * rank), so the starts are dealt over the devices, longest first by estimated cost

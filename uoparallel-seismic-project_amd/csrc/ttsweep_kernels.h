@@ -196,6 +196,23 @@ hipError_t launch_locate_final(const float *const *boxes, int K, const double *p
 hipError_t launch_locate_volume(const float *const *boxes, int K, int N, const double *picks, const double *weights,
                                 const double *invw, const int *vev, double *const *vol, int nvol, hipStream_t st);
 
+// confidence regions of located events (ttsweep_locate.hip).  check: lim[e * L + l], the exclusive limit on the bits
+// of J of level l (0: the empty region), limmax[e] their greatest, flag[e] (bit 0 a NaN or negative m, bit 1 a NaN or
+// negative delta); init: the n = nevent * L accumulators (g_sum [n][10], g_t0 [n][2] keys, g_box [n][6]) at their
+// empty-region values; search: events e0 .. e0 + ne - 1 (at most 65535 * 8) added to them; final: the accumulators
+// to the caller's arrays (each may be nullptr)
+hipError_t launch_confidence_check(int nevent, int L, const double *m, const double *delta, unsigned long long *lim,
+                                   unsigned long long *limmax, int *flag, hipStream_t st);
+hipError_t launch_confidence_init(long long n, int nx, int ny, int nz, unsigned long long *g_sum,
+                                  unsigned long long *g_t0, int *g_box, hipStream_t st);
+hipError_t launch_confidence_search(const float *const *boxes, int K, int N, int ny, int nz, const double *picks,
+                                    const double *weights, const double *invw, int e0, int ne, int L,
+                                    const unsigned long long *lim, const unsigned long long *limmax,
+                                    unsigned long long *g_sum, unsigned long long *g_t0, int *g_box, hipStream_t st);
+hipError_t launch_confidence_final(long long n, const unsigned long long *g_sum, const unsigned long long *g_t0,
+                                   const int *g_box, long long *count, long long *sum, long long *sum2, int *lo,
+                                   int *hi, double *t0_lo, double *t0_hi, hipStream_t st);
+
 #ifdef TTSWEEP_TILE_PROFILE
 void tile_prof_dump();   // prints and clears the phase counters of tile_sweep_kernel
 #endif

@@ -270,7 +270,218 @@ locate_volume_kernel(const float *const *__restrict__ boxes, int K, int N, const
     vol[blockIdx.y][x] = key < LOC_INF ? key : LOC_INF;
 }
 
+// ---- confidence regions (include/ttsweep.h, "locate confidence") ----
+// R(e, l) = { x admissible and J(x) <= m[e] + delta[e][l] }, summarised without a volume.  J >= +0 on every cell, so
+// "admissible and J <= thr" is one unsigned compare of the bits of J with an exclusive limit:
+//   lim[e][l] = min(bits(thr) + 1, bits(+INF)), 0 for the empty region (m[e] = +INF); limmax[e] the greatest of them
+//   confidence_check_kernel   one lane per event: refuses a NaN or negative m / delta on the bits, forms the limits
+//   confidence_init_kernel    the accumulators of every (e, l) at their empty-region values
+//   confidence_search_kernel  the cell and event loops of locate_search_kernel with loc_misfit, the same J bits.  Per
+//                             (cell step, event) one wave vote on key < limmax[e]; only when a lane is inside do the
+//                             lanes inside level l add to the block's accumulators in LDS.  Those atomics have a
+//                             wave-uniform address, which the compiler (its atomic optimizer, -S) turns into a
+//                             scalar pass over the lanes inside (v_readlane per lane) and one atomic of one lane:
+//                             the cost follows the number of cells inside, not the wave width.  At the end of the
+//                             block the (event, level) pairs that met a cell add their 18 values to the global
+//                             accumulators.
+//   confidence_final_kernel   one lane per (e, l): the accumulators to the caller's arrays, t0 keys back to doubles
+// Every accumulator is an integer sum, minimum or maximum (t0 through its totalOrder key), so the result does not
+// depend on the order of the atomics: no float atomics, no partials, no fixed final order.
+constexpr int CONF_LMAX = 4;
+constexpr int CONF_NSUM = 10;      // count, x, y, z, xx, yy, zz, xy, xz, yz
+
+// IEEE totalOrder of doubles as an unsigned order of keys, and back
+__device__ __forceinline__ unsigned long long conf_t0_key(double t)
+{
+    const unsigned long long u = dbits(t);
+    return u >> 63 ? ~u : u | 0x8000000000000000ULL;
+}
+
+__device__ __forceinline__ unsigned long long conf_t0_bits(unsigned long long k)
+{
+    return k >> 63 ? k & 0x7fffffffffffffffULL : ~k;
+}
+
+// flag[e]: bit 0 a NaN or negative m, bit 1 a NaN or negative delta
+__global__ void __launch_bounds__(LOC_BLOCK)
+confidence_check_kernel(int nevent, int L, const double *__restrict__ m, const double *__restrict__ delta,
+                        unsigned long long *__restrict__ lim, unsigned long long *__restrict__ limmax,
+                        int *__restrict__ flag)
+{
+    const int e = blockIdx.x * LOC_BLOCK + threadIdx.x;
+    if (e >= nevent) return;
+    auto bad = [](unsigned long long u) {      // NaN, or below zero (-0.0 is zero)
+        return (u & 0x7fffffffffffffffULL) > LOC_INF || (u >> 63 && (u << 1) != 0);
+    };
+    const unsigned long long mb = dbits(m[e]);
+    int f = bad(mb) ? 1 : 0;
+    for (int l = 0; l < L; l++)
+        if (bad(dbits(delta[(long long)e * L + l]))) f |= 2;
+    unsigned long long top = 0;
+    for (int l = 0; l < L; l++) {               // a refused or never located event: the empty region at every level
+        unsigned long long t = 0;
+        if (!f && mb != LOC_INF) {
+            unsigned long long tb = dbits(m[e] + delta[(long long)e * L + l]);
+            if ((tb << 1) == 0) tb = 0;
+            t = tb >= LOC_INF ? LOC_INF : tb + 1;
+        }
+        lim[(long long)e * L + l] = t;
+        top = t > top ? t : top;
+    }
+    limmax[e] = top;
+    flag[e] = f;
+}
+
+__global__ void __launch_bounds__(LOC_BLOCK)
+confidence_init_kernel(long long n, int nx, int ny, int nz, unsigned long long *__restrict__ g_sum,
+                       unsigned long long *__restrict__ g_t0, int *__restrict__ g_box)
+{
+    const long long p = (long long)blockIdx.x * LOC_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    for (int q = 0; q < CONF_NSUM; q++) g_sum[p * CONF_NSUM + q] = 0;
+    g_t0[p * 2] = ~0ULL;
+    g_t0[p * 2 + 1] = 0;
+    g_box[p * 6] = nx;
+    g_box[p * 6 + 1] = ny;
+    g_box[p * 6 + 2] = nz;
+    g_box[p * 6 + 3] = g_box[p * 6 + 4] = g_box[p * 6 + 5] = -1;
+}
+
+// blockIdx.x: a tile of LOC_C * LOC_BLOCK cells; blockIdx.y: LOC_ET events from e0
+template <int KR>
+__global__ void __launch_bounds__(LOC_BLOCK)
+confidence_search_kernel(const float *const *__restrict__ boxes, int K, int N, int ny, int nz,
+                         const double *__restrict__ picks, const double *__restrict__ weights,
+                         const double *__restrict__ invw, int e0, int ne, int L,
+                         const unsigned long long *__restrict__ lim, const unsigned long long *__restrict__ limmax,
+                         unsigned long long *__restrict__ g_sum, unsigned long long *__restrict__ g_t0,
+                         int *__restrict__ g_box)
+{
+    __shared__ unsigned long long s_sum[LOC_ET * CONF_LMAX][CONF_NSUM];
+    __shared__ unsigned long long s_t0[LOC_ET * CONF_LMAX][2];
+    __shared__ int s_box[LOC_ET * CONF_LMAX][6];
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.x;
+    const int eb = blockIdx.y * LOC_ET;                 // first event of the block, relative to e0
+    const int net = min(LOC_ET, ne - eb);
+    if (tid < LOC_ET * CONF_LMAX) {
+        for (int q = 0; q < CONF_NSUM; q++) s_sum[tid][q] = 0;
+        s_t0[tid][0] = ~0ULL;
+        s_t0[tid][1] = 0;
+        s_box[tid][0] = s_box[tid][1] = s_box[tid][2] = 0x7fffffff;
+        s_box[tid][3] = s_box[tid][4] = s_box[tid][5] = -1;
+    }
+    __syncthreads();
+    const long long base = (long long)tile * (LOC_C * LOC_BLOCK);
+    const int nj = (int)min((long long)LOC_C, (N - base + LOC_BLOCK - 1) / LOC_BLOCK);
+    const int nyz = ny * nz;
+    for (int j = 0; j < nj; j++) {
+        const long long xl = base + (long long)j * LOC_BLOCK + tid;
+        const bool in = xl < N;
+        const int x = in ? (int)xl : N - 1;
+        double tr[KR > 0 ? KR : 1];
+        if constexpr (KR > 0) {
+#pragma unroll
+            for (int k = 0; k < KR; k++) tr[k] = k < K ? (double)boxes[k][x] : 0.0;
+        }
+        for (int i = 0; i < net; i++) {
+            const int e = __builtin_amdgcn_readfirstlane(e0 + eb + i);
+            const double *o = picks + (long long)e * K;
+            const double *w = weights ? weights + (long long)e * K : nullptr;
+            double t0;
+            const double J = KR > 0 ? loc_misfit<KR>([&](int k) { return tr[k]; }, K, o, w, invw[e], t0)
+                                    : loc_misfit<0>([&](int k) { return (double)boxes[k][x]; }, K, o, w, invw[e], t0);
+            const unsigned long long key = dbits(J);
+            if (!__any(in && key < limmax[e])) continue;        // the common case: no lane of the wave is inside
+            const unsigned long long cx = (unsigned)(x / nyz), cy = (unsigned)(x % nyz / nz), cz = (unsigned)(x % nz);
+            const unsigned long long tk = conf_t0_key(t0);
+            for (int l = 0; l < L; l++) {
+                if (!(in && key < lim[(long long)e * L + l])) continue;
+                const int a = i * CONF_LMAX + l;                // wave-uniform: one atomic of one lane per value
+                atomicAdd(&s_sum[a][0], 1ULL);
+                atomicAdd(&s_sum[a][1], cx);
+                atomicAdd(&s_sum[a][2], cy);
+                atomicAdd(&s_sum[a][3], cz);
+                atomicAdd(&s_sum[a][4], cx * cx);
+                atomicAdd(&s_sum[a][5], cy * cy);
+                atomicAdd(&s_sum[a][6], cz * cz);
+                atomicAdd(&s_sum[a][7], cx * cy);
+                atomicAdd(&s_sum[a][8], cx * cz);
+                atomicAdd(&s_sum[a][9], cy * cz);
+                atomicMin(&s_t0[a][0], tk);
+                atomicMax(&s_t0[a][1], tk);
+                atomicMin(&s_box[a][0], (int)cx);
+                atomicMin(&s_box[a][1], (int)cy);
+                atomicMin(&s_box[a][2], (int)cz);
+                atomicMax(&s_box[a][3], (int)cx);
+                atomicMax(&s_box[a][4], (int)cy);
+                atomicMax(&s_box[a][5], (int)cz);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid >= net * CONF_LMAX || (tid & (CONF_LMAX - 1)) >= L || s_sum[tid][0] == 0) return;
+    const long long p = (long long)(e0 + eb + tid / CONF_LMAX) * L + (tid & (CONF_LMAX - 1));
+    for (int q = 0; q < CONF_NSUM; q++) atomicAdd(&g_sum[p * CONF_NSUM + q], s_sum[tid][q]);
+    atomicMin(&g_t0[p * 2], s_t0[tid][0]);
+    atomicMax(&g_t0[p * 2 + 1], s_t0[tid][1]);
+    for (int q = 0; q < 3; q++) {
+        atomicMin(&g_box[p * 6 + q], s_box[tid][q]);
+        atomicMax(&g_box[p * 6 + 3 + q], s_box[tid][3 + q]);
+    }
+}
+
+// one lane per (e, l); every output may be nullptr
+__global__ void __launch_bounds__(LOC_BLOCK)
+confidence_final_kernel(long long n, const unsigned long long *__restrict__ g_sum,
+                        const unsigned long long *__restrict__ g_t0, const int *__restrict__ g_box,
+                        long long *__restrict__ count, long long *__restrict__ sum, long long *__restrict__ sum2,
+                        int *__restrict__ lo, int *__restrict__ hi, unsigned long long *__restrict__ t0_lo,
+                        unsigned long long *__restrict__ t0_hi)
+{
+    const long long p = (long long)blockIdx.x * LOC_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const unsigned long long *s = g_sum + p * CONF_NSUM;
+    const bool any = s[0] != 0;
+    if (count) count[p] = (long long)s[0];
+    for (int q = 0; q < 3; q++) {
+        if (sum) sum[p * 3 + q] = (long long)s[1 + q];
+        if (lo) lo[p * 3 + q] = g_box[p * 6 + q];
+        if (hi) hi[p * 3 + q] = g_box[p * 6 + 3 + q];
+    }
+    if (sum2)
+        for (int q = 0; q < 6; q++) sum2[p * 6 + q] = (long long)s[4 + q];
+    if (t0_lo) t0_lo[p] = any ? conf_t0_bits(g_t0[p * 2]) : LOC_INF;
+    if (t0_hi) t0_hi[p] = any ? conf_t0_bits(g_t0[p * 2 + 1]) : LOC_INF | 0x8000000000000000ULL;
+}
+
 int locate_tile_cells() { return LOC_C * LOC_BLOCK; }
+
+hipError_t launch_confidence_check(int nevent, int L, const double *m, const double *delta, unsigned long long *lim,
+                                   unsigned long long *limmax, int *flag, hipStream_t st)
+{
+    hipLaunchKernelGGL(confidence_check_kernel, dim3((nevent + LOC_BLOCK - 1) / LOC_BLOCK), dim3(LOC_BLOCK), 0, st,
+                       nevent, L, m, delta, lim, limmax, flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_confidence_init(long long n, int nx, int ny, int nz, unsigned long long *g_sum,
+                                  unsigned long long *g_t0, int *g_box, hipStream_t st)
+{
+    hipLaunchKernelGGL(confidence_init_kernel, dim3((unsigned)((n + LOC_BLOCK - 1) / LOC_BLOCK)), dim3(LOC_BLOCK), 0,
+                       st, n, nx, ny, nz, g_sum, g_t0, g_box);
+    return hipGetLastError();
+}
+
+hipError_t launch_confidence_final(long long n, const unsigned long long *g_sum, const unsigned long long *g_t0,
+                                   const int *g_box, long long *count, long long *sum, long long *sum2, int *lo,
+                                   int *hi, double *t0_lo, double *t0_hi, hipStream_t st)
+{
+    hipLaunchKernelGGL(confidence_final_kernel, dim3((unsigned)((n + LOC_BLOCK - 1) / LOC_BLOCK)), dim3(LOC_BLOCK), 0,
+                       st, n, g_sum, g_t0, g_box, count, sum, sum2, lo, hi, (unsigned long long *)t0_lo,
+                       (unsigned long long *)t0_hi);
+    return hipGetLastError();
+}
 
 hipError_t launch_locate_check(int K, int nevent, const double *picks, const double *weights, double *invw, int *flag,
                                hipStream_t st)
@@ -336,6 +547,30 @@ hipError_t launch_locate_volume(const float *const *boxes, int K, int N, const d
                                 invw, vev, v); break;
     default: hipLaunchKernelGGL(locate_volume_kernel<0>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
                                 invw, vev, v); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_confidence_search(const float *const *boxes, int K, int N, int ny, int nz, const double *picks,
+                                    const double *weights, const double *invw, int e0, int ne, int L,
+                                    const unsigned long long *lim, const unsigned long long *limmax,
+                                    unsigned long long *g_sum, unsigned long long *g_t0, int *g_box, hipStream_t st)
+{
+    if (ne <= 0 || N <= 0) return hipSuccess;
+    const int ntiles = (int)(((long long)N + LOC_C * LOC_BLOCK - 1) / (LOC_C * LOC_BLOCK));
+    const dim3 grid(ntiles, (ne + LOC_ET - 1) / LOC_ET);
+    if (grid.y > 65535 || L < 1 || L > CONF_LMAX) return hipErrorInvalidValue;
+    switch (loc_kr(K)) {
+    case 8: hipLaunchKernelGGL(confidence_search_kernel<8>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, ny, nz, picks,
+                               weights, invw, e0, ne, L, lim, limmax, g_sum, g_t0, g_box); break;
+    case 16: hipLaunchKernelGGL(confidence_search_kernel<16>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, ny, nz, picks,
+                                weights, invw, e0, ne, L, lim, limmax, g_sum, g_t0, g_box); break;
+    case 24: hipLaunchKernelGGL(confidence_search_kernel<24>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, ny, nz, picks,
+                                weights, invw, e0, ne, L, lim, limmax, g_sum, g_t0, g_box); break;
+    case 32: hipLaunchKernelGGL(confidence_search_kernel<32>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, ny, nz, picks,
+                                weights, invw, e0, ne, L, lim, limmax, g_sum, g_t0, g_box); break;
+    default: hipLaunchKernelGGL(confidence_search_kernel<0>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, ny, nz, picks,
+                                weights, invw, e0, ne, L, lim, limmax, g_sum, g_t0, g_box); break;
     }
     return hipGetLastError();
 }

@@ -279,6 +279,58 @@ class TravelTimeSolver:
         xyz[c < 0] = -1
         return Locations(cell, xyz, misfit, t0, vols)
 
+    def locate_confidence(self, tt, picks, weights, misfit, delta) -> "ConfidenceRegions":
+        """ttsweep_locate_confidence_device: per event and level the region of admissible cells with
+        J <= misfit[e] + delta[e, l], summarised without a misfit volume (include/ttsweep.h, "locate confidence").
+        tt, picks, weights as for locate (weights None: every weight 1.0).  misfit: float64 [E] on the device or
+        numpy, normally Locations.misfit.  delta: a scalar, [L] or [E, L] (1 <= L <= 4), broadcast to [E, L]
+        float64; inf is allowed (every admissible cell)."""
+        import torch
+        _require(isinstance(tt, torch.Tensor) and tt.dim() == 4, "tt: torch float32 [K, nx, ny, nz]")
+        K = int(tt.shape[0])
+        self._require_device_tensor(tt, (K,) + self.shape, "station boxes")
+        dev = tt.device
+
+        def on_device(a, what):
+            if isinstance(a, np.ndarray):
+                _require(a.dtype == np.float64, f"{what}: float64")
+                a = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            _require(isinstance(a, torch.Tensor) and a.dtype == torch.float64 and a.device == dev,
+                     f"{what}: float64 tensor on {dev} or numpy array")
+            return a.contiguous()
+
+        picks = on_device(picks, "picks")
+        _require(picks.dim() == 2 and picks.shape[1] == K and picks.shape[0] >= 1,
+                 f"picks: shape {tuple(picks.shape)}, want [E, {K}]")
+        E = int(picks.shape[0])
+        if weights is not None:
+            weights = on_device(weights, "weights")
+            _require(tuple(weights.shape) == (E, K), f"weights: shape {tuple(weights.shape)}, want {(E, K)}")
+        misfit = on_device(misfit, "misfit")
+        _require(tuple(misfit.shape) == (E,), f"misfit: shape {tuple(misfit.shape)}, want {(E,)}")
+        if not isinstance(delta, torch.Tensor):
+            delta = np.atleast_1d(np.asarray(delta, dtype=np.float64))
+        delta = on_device(delta, "delta")
+        if delta.dim() < 2:
+            delta = delta.reshape(1, -1)
+        _require(delta.dim() == 2 and 1 <= delta.shape[1] <= 4 and delta.shape[0] in (1, E),
+                 f"delta: shape {tuple(delta.shape)}, want a scalar, [L] or [{E}, L] with 1 <= L <= 4")
+        L = int(delta.shape[1])
+        delta = delta.expand(E, L).contiguous()
+
+        def out(dtype, *tail):
+            return torch.empty((E, L) + tail, dtype=dtype, device=dev)
+
+        r = ConfidenceRegions(out(torch.int64), out(torch.int64, 3), out(torch.int64, 6), out(torch.int32, 3),
+                              out(torch.int32, 3), out(torch.float64), out(torch.float64), self.shape)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.ttsweep_locate_confidence_device(
+            self._ctx, K, self._box_pointers(tt, K), E, picks.data_ptr(),
+            None if weights is None else weights.data_ptr(), misfit.data_ptr(), L, delta.data_ptr(),
+            r.count.data_ptr(), r.sum.data_ptr(), r.sum2.data_ptr(), r.lo.data_ptr(), r.hi.data_ptr(),
+            r.t0_lo.data_ptr(), r.t0_hi.data_ptr()), "ttsweep_locate_confidence_device")
+        return r
+
     def stats(self) -> dict:
         st = Stats()
         _check(self._L.ttsweep_get_stats(self._ctx, C.byref(st)), "ttsweep_get_stats")
@@ -319,6 +371,59 @@ class Locations:
 
     def __len__(self):
         return len(self.cell)
+
+
+def _host(a):
+    return a if isinstance(a, np.ndarray) else a.cpu().numpy()
+
+
+@dataclass
+class ConfidenceRegions:
+    """Regions of TravelTimeSolver.locate_confidence (include/ttsweep.h, "locate confidence"), E events, L levels:
+    the admissible cells with J <= misfit[e] + delta[e, l].  All on the device.
+      count        [E,L] int64: cells in the region
+      sum          [E,L,3] int64: sum of x, y, z over it
+      sum2         [E,L,6] int64: sum of xx, yy, zz, xy, xz, yz
+      lo, hi       [E,L,3] int32: its bounding box, inclusive; (nx, ny, nz) and (-1, -1, -1) when empty
+      t0_lo, t0_hi [E,L] float64: the range of the origin time over it; +inf and -inf when empty
+      shape        (nx, ny, nz) of the grid
+    centroid(), covariance() and open() are computed on the host in float64 (numpy)."""
+    count: "object"
+    sum: "object"
+    sum2: "object"
+    lo: "object"
+    hi: "object"
+    t0_lo: "object"
+    t0_hi: "object"
+    shape: tuple
+
+    def __len__(self):
+        return len(self.count)
+
+    def centroid(self):
+        """[E,L,3] float64: sum / count in cells, the sub-cell hypocentre estimate; NaN where the region is empty."""
+        n = _host(self.count).astype(np.float64)[..., None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return _host(self.sum).astype(np.float64) / n
+
+    def covariance(self):
+        """[E,L,3,3] float64 in cells^2: (sum_ab - sum_a * (sum_b / n)) / n, each operation rounded once; symmetric
+        (an off-diagonal pair is computed once); NaN where the region is empty."""
+        n = _host(self.count).astype(np.float64)
+        s = _host(self.sum).astype(np.float64)
+        q = _host(self.sum2).astype(np.float64)
+        cov = np.empty(n.shape + (3, 3))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for i, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+                cov[..., a, b] = cov[..., b, a] = (q[..., i] - s[..., a] * (s[..., b] / n)) / n
+        return cov
+
+    def open(self):
+        """[E,L] bool: the bounding box touches a face of the grid, so the region is cut off by the model boundary
+        and its statistics understate the uncertainty.  False where the region is empty."""
+        lo, hi = _host(self.lo), _host(self.hi)
+        top = np.asarray(self.shape, dtype=lo.dtype) - 1
+        return (_host(self.count) > 0) & np.any((lo == 0) | (hi == top), axis=-1)
 
 
 class FrechetOperator:
