@@ -11,6 +11,7 @@ import pytest
 
 from conftest import GOLDEN
 import confidence_reference as R
+import locate_cases as Cs
 import locate_reference as L
 
 INF = np.float32(np.inf)
@@ -203,3 +204,74 @@ def test_locate_confidence_checks_arguments_before_the_library(pkg):
     sol.shape, sol.device = (2, 2, 2), 0
     with pytest.raises(pkg.TTSweepError):
         sol.locate_confidence(np.zeros((1, 2, 2, 2), np.float32), np.zeros((1, 1)), None, np.zeros(1), 1.0)
+
+
+# ---- the claims of the confidence cases of locate_cases.py, checked with the restatement alone ----
+
+def test_k_edge_regions_are_not_trivial():
+    """Every (K, N) of the K-edge cases, both calls, the sparse level: the restatement's region is neither empty nor
+    every admissible cell for at least three quarters of the events.  The restatement gives 1253 of 1456 here (counts 5 ... 7592): every event
+    on the seven grids of 255 cells and more but the K = 1 events with unit weights (J = +0 at every cell), none on
+    the grid of one cell, where no region can be.  Level 0 holds the located cell and delta = +inf every admissible cell."""
+    inside = total = 0
+    lo, hi = 10 ** 9, 0
+    for N in Cs.N_SHAPES:
+        for K in Cs.K_EDGES:
+            c = Cs.k_edge_case(K, N)
+            for call in ("weighted", "none"):
+                d = c[call]
+                assert R.check(d["m"], d["delta"]) is None
+                got = Cs.confidence(c["tt"], d["picks"], d["weights"], d["m"], d["delta"])["count"]
+                ok = (got[:, 1] > 0) & (got[:, 1] < got[:, 2])       # full: every admissible cell
+                inside, total = inside + int(ok.sum()), total + len(ok)
+                if N > 1 and (K > 1 or call == "weighted"):      # K = 1 with unit weights: J = +0 everywhere
+                    lo, hi = min(lo, int(got[:, 1].min())), max(hi, int(got[:, 1].max()))
+                    assert np.all(got[:, 0] >= 1) and np.all(got[:, 0] <= got[:, 1]) and np.all(got[:, 1] < got[:, 2])
+    print("sparse regions neither empty nor full:", inside, "of", total, "counts", lo, "...", hi)
+    assert inside >= 0.75 * total
+
+
+def test_cap_case_levels():
+    tt, picks, w, delta = Cs.cap_case()
+    _, m, _, _ = Cs.locate_rows(tt, picks, w)
+    assert R.check(m, delta) is None and delta.shape == (Cs.CAP_P, 4)
+    got = Cs.confidence(tt, picks, w, m, delta)["count"]
+    assert np.all(got[:, 0] >= 1) and np.all(np.diff(got, axis=1) >= 0) and len(np.unique(got[:, 2])) >= 4
+
+
+def test_thresholds_at_the_largest_finite_double():
+    tt, picks, w, m, delta = Cs.conf_range_case("thr_largest_finite")
+    assert R.check(m, delta) is None
+    with np.errstate(all="ignore"):
+        thr = m[:, None] + delta
+    inf_bits = Cs.u64(np.inf)
+    for e, l in ((0, 0), (1, 0), (1, 2), (2, 0), (3, 0)):       # (1, 0) gets there by rounding up
+        assert thr[e, l] == Cs.DBL_MAX and Cs.u64(thr[e, l]) + 1 == inf_bits, (e, l)
+    assert m[1] + delta[1, 0] > m[1] and delta[1, 0] < 2.0 ** 971
+    assert thr[0, 2] == np.inf and thr[2, 2] == np.inf
+    got = Cs.confidence(tt, picks, w, m, delta)["count"]
+    adm = int(np.all(np.isfinite(tt), axis=0).sum())
+    J, _ = Cs.misfit(tt, picks[0])
+    assert m[2] == J[J < np.inf].max() and np.all(got[:3] == adm) and got[3].tolist() == [adm, adm, 0]
+
+
+def test_thresholds_in_the_subnormal_range():
+    tt, picks, w, m, delta = Cs.conf_range_case("thr_subnormal")
+    assert R.check(m, delta) is None
+    thr = m[:, None] + delta
+    assert np.all(thr > 0) and np.all(thr < Cs.DBL_TINY) and np.all(delta[:, 1:] > 0) and np.all(m < Cs.DBL_TINY)
+    got = Cs.confidence(tt, picks, w, m, delta)["count"]
+    adm = int((Cs.misfit(tt, picks[0], w[0])[0] < np.inf).sum())
+    assert np.all(got[:, 0] >= 1) and np.all(got[:, 2] > got[:, 0]) and np.all(got[:, 3] > got[:, 2])
+    assert np.all(got[:, 3] < adm)
+
+
+def test_thresholds_one_ulp_around_a_cell():
+    tt, picks, w, m, delta = Cs.conf_range_case("thr_one_ulp")
+    assert R.check(m, delta) is None and np.all(delta == 0)
+    J, _ = Cs.misfit(tt, picks[0], w[0])
+    got = Cs.confidence(tt, picks, w, m, delta)["count"][:, 0].reshape(-1, 3)
+    at = m.reshape(-1, 3)[:, 1]
+    for (below, exact, above), Jx in zip(got.tolist(), at):
+        assert exact == above == int((J <= Jx).sum()) and exact - below == int((J == Jx).sum()) >= 1
+    assert got[0, 0] == 0 and got[-1, 1] == J.size

@@ -11,6 +11,7 @@ import pytest
 
 from conftest import GOLDEN, Golden
 import confidence_reference as R
+import locate_cases as Cs
 
 pytestmark = pytest.mark.gpu
 
@@ -334,3 +335,81 @@ def test_a_grid_whose_second_moments_could_overflow_is_refused(P):
                                                          *([None] * 6))
             assert rc < 0 and "overflow" in P._lib.last_error()
             assert int(count[0, 0]) == 77
+
+
+# ---- the cases of locate_cases.py (their claims are checked by the CPU tier, tests/test_confidence_cpu.py and
+# tests/test_locate_cpu.py) ----
+def check_regions(sol, tt, picks, weights, m, delta, what=""):
+    """locate_confidence at the levels m, delta == the restatement, every output; returns the host dict"""
+    import torch
+    tdev = torch.from_numpy(np.ascontiguousarray(tt, dtype=F32)).to(dev())
+    got = host(sol.locate_confidence(tdev, picks, weights, np.ascontiguousarray(m), np.ascontiguousarray(delta)))
+    assert_same(got, Cs.confidence(tt, picks, weights, m, delta), what)
+    return got
+
+
+def test_more_events_than_one_launch_takes(P):
+    """2 x 3 x 2 cells, K = 2, 65535 * 8 + 3 events that repeat 97 distinct rows, four levels: the last three events
+    are the second launch of the search.  The distinct rows against the restatement, every event against its row."""
+    import torch
+    tt, rows_p, rows_w, rows_d = Cs.cap_case()
+    E, period = Cs.CAP_E, Cs.CAP_P
+    assert E - Cs.CAP == 3
+    _, rows_m, _, _ = Cs.locate_rows(tt, rows_p, rows_w)
+    picks, w, m, delta = (Cs.periodic(a, E) for a in (rows_p, rows_w, rows_m, rows_d))
+    with P.TravelTimeSolver(Cs.CAP_SHAPE, star818(P)) as sol:
+        got = host(sol.locate_confidence(torch.from_numpy(tt).to(dev()), picks, w, m, delta))
+    assert_same({f: v[:period] for f, v in got.items()}, Cs.confidence(tt, rows_p, rows_w, rows_m, rows_d), "rows")
+    first = np.arange(E) % period
+    assert_same(got, {f: v[first] for f, v in got.items()}, "every event against its row")
+    assert np.all(got["count"][-3:, 0] >= 1)
+
+
+def test_regions_on_a_grid_of_many_tiles(P):
+    """17 x 59 x 4095 (1003 tiles, the last partial): six rows of the planted case, among them the minimum at the
+    last cell, the tie of one cell in every tile and an unplanted row; levels 0, 0.5 (the decoy), 4.5 (the cells
+    planted for the neighbouring rows) and +inf."""
+    rows = (1, 7, 14, 16, 17, 50)
+    tt = np.array(Cs.big_box())
+    picks = Cs.big_rows("unit")[0][list(rows)]
+    ref = Cs.big_reference("unit", rows)
+    m = np.array([ref[r][1] for r in rows])
+    with P.TravelTimeSolver(Cs.BIG_SHAPE, star818(P)) as sol:
+        got = check_regions(sol, tt, picks, None, m, np.tile([0.0, 0.5, 4.5, np.inf], (len(rows), 1)), "big")
+    assert got["count"][:, 0].tolist() == [ref[r][5] for r in rows] and got["count"][4, 0] == 1003
+    assert np.all(got["count"][:, 3] == tt[0].size) and np.all(got["count"][:5, 2] > got["count"][:5, 1])
+
+
+@pytest.mark.parametrize("N", sorted(Cs.N_SHAPES))
+def test_full_and_just_over_full_register_widths(P, N):
+    """K in 1, 2, 7 ... 33 around every register instance on a grid of N cells with all three axes in play: the
+    weighted events of every pattern and the events with weights NULL, levels 0, a sparse one and +inf at the
+    restatement's minimum."""
+    with P.TravelTimeSolver(Cs.N_SHAPES[N], star818(P)) as sol:
+        for K in Cs.K_EDGES:
+            c = Cs.k_edge_case(K, N)
+            for call in ("weighted", "none"):
+                d = c[call]
+                got = check_regions(sol, c["tt"], d["picks"], d["weights"], d["m"], d["delta"], f"K={K} N={N} {call}")
+                assert np.all(got["count"][:, 0] >= 1)
+
+
+@pytest.mark.parametrize("route", Cs.RANGE_ROUTES)
+def test_double_range_of_picks_and_weights(P, route):
+    tt, picks, w = Cs.range_case(route)
+    _, m, _, _ = Cs.locate_rows(tt, picks, w)
+    delta = np.tile([0.0, 1.0, 1e300, np.inf], (len(picks), 1))
+    with P.TravelTimeSolver(Cs.RANGE_SHAPE, star818(P)) as sol:
+        got = check_regions(sol, tt, picks, w, m, delta, route)
+        assert np.all((got["count"][:, 0] >= 1) == (m < np.inf))
+        check_regions(sol, tt, picks, w, np.zeros(len(picks)), delta, route + ", m = 0")
+
+
+@pytest.mark.parametrize("name", Cs.CONF_RANGE_CASES)
+def test_double_range_of_levels(P, name):
+    """m + delta at the largest finite double (exactly and by rounding), in the subnormal range, and one ulp below,
+    at and one ulp above the J of a cell."""
+    tt, picks, w, m, delta = Cs.conf_range_case(name)
+    assert R.check(m, delta) is None
+    with P.TravelTimeSolver(Cs.RANGE_SHAPE, star818(P)) as sol:
+        check_regions(sol, tt, picks, w, m, delta, name)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, Golden
+import locate_cases as Cs
 import locate_reference as L
 
 pytestmark = pytest.mark.gpu
@@ -53,19 +54,24 @@ def star818(P):
     return P.inputs.make_fs(P.inputs.read_triples(P.inputs.star_path("818")))
 
 
-def check_locate(P, tt, picks, weights=None, vol_events=(), ref_events=None, what=""):
-    """locate on the device == the restatement (every event, or ref_events), bit for bit; returns the result."""
+def check_locate(P, tt, picks, weights=None, vol_events=(), ref_events=None, what="", sol=None):
+    """locate on the device == the restatement (every event, or ref_events), bit for bit; returns the result.  sol: a
+    solver of the boxes' shape to use (one is made when None)."""
     import torch
     tt = np.ascontiguousarray(tt, dtype=F32)
     shape = tt.shape[1:]
-    with P.TravelTimeSolver(shape, star818(P)) as sol:
-        tdev = torch.from_numpy(tt).to(dev())
-        res = sol.locate(tdev, picks, weights, misfit_events=list(vol_events) or None)
+    if sol is None:
+        with P.TravelTimeSolver(shape, star818(P)) as own:
+            return check_locate(P, tt, picks, weights, vol_events, ref_events, what, own)
+    tdev = torch.from_numpy(tt).to(dev())
+    res = sol.locate(tdev, picks, weights, misfit_events=list(vol_events) or None)
     assert res.cell.dtype == torch.int32 and res.cell.device == dev() and res.misfit.dtype == torch.float64
     cell, mis, t0 = res.cell.cpu().numpy(), res.misfit.cpu().numpy(), res.t0.cpu().numpy()
     idx = np.arange(len(picks)) if ref_events is None else np.asarray(ref_events)
     w = None if weights is None else np.asarray(weights)[idx]
-    rc, rm, rt, rv = L.locate(tt, np.asarray(picks)[idx], w, volumes=[i for i, e in enumerate(idx) if e in vol_events])
+    with np.errstate(all="ignore"):          # the float-range cases overflow on purpose
+        rc, rm, rt, rv = L.locate(tt, np.asarray(picks)[idx], w,
+                                  volumes=[i for i, e in enumerate(idx) if e in vol_events])
     assert np.array_equal(cell[idx], rc), what
     assert np.array_equal(u64(mis[idx]), u64(rm)), what
     nan = np.isnan(rt)
@@ -303,3 +309,98 @@ def test_located_cells_feed_the_frechet_operator(P):
         op = sol.frechet_operator(stations, tt, xyz)
         want = tt.reshape(8, -1)[:, loc.cell.to(torch.int64)].reshape(-1).cpu()
         assert torch.equal(op.t_recv.view(torch.int32), want.view(torch.int32))
+
+
+# ---- the cases of locate_cases.py (their claims are checked by the CPU tier, tests/test_locate_cpu.py) ----
+def outputs(res):
+    return res.cell.cpu().numpy(), res.misfit.cpu().numpy(), res.t0.cpu().numpy()
+
+
+def assert_periodic(cell, mis, t0, period, what):
+    """every output equals the output of its row: event e against event e % period"""
+    first = np.arange(len(cell)) % period
+    assert np.array_equal(cell, cell[first]), what
+    assert np.array_equal(u64(mis), u64(mis[first])) and np.array_equal(u64(t0), u64(t0[first])), what
+
+
+@pytest.mark.parametrize("variant", ["unit", "weighted"])
+def test_second_and_third_batches_on_a_grid_of_many_tiles(P, variant):
+    """17 x 59 x 4095 (1003 tiles, the last partial), K = 2, 2 * 16727 + 5 events that repeat 97 distinct rows: three
+    batches of ttsweep_locate_device, each ending in a partial event block (the formula of Cs.batches mirrors
+    LOC_PARTIALS and LOC_ET).  The distinct rows against the restatement bit for bit, every event against its row,
+    the events around each batch edge again as calls of their own, the planted ties at their smallest index, one
+    misfit volume of the last batch."""
+    import torch
+    E, period = Cs.BIG_E, Cs.BIG_P
+    ntiles, eb, starts = Cs.batches(Cs.BIG_SHAPE, E)
+    assert len(starts) >= 3 and eb % Cs.ET != 0 and ntiles > 3 * 256 and starts[-1] + eb > E
+    tt = np.array(Cs.big_box())
+    rows_p, rows_w = Cs.big_rows(variant)
+    picks, w = Cs.periodic(rows_p, E), Cs.periodic(rows_w, E)
+    ref = Cs.big_reference(variant)
+    vol_e = E - 2
+    with P.TravelTimeSolver(Cs.BIG_SHAPE, star818(P)) as sol:
+        tdev = torch.from_numpy(tt).to(dev())
+        pd = torch.from_numpy(picks).to(dev())
+        wd = None if w is None else torch.from_numpy(w).to(dev())
+        res = sol.locate(tdev, pd, wd, misfit_events=[vol_e])
+        cell, mis, t0 = outputs(res)
+        for r, (c, m, t) in ((r, v[:3]) for r, v in ref.items()):
+            assert (cell[r], u64(mis[r]), u64(t0[r])) == (c, u64(m), u64(t)), (variant, "row", r)
+        assert_periodic(cell, mis, t0, period, variant)
+        for r, (kind, cells, _) in Cs.big_plants().items():
+            assert np.all(cell[r::period] == min(cells)), (variant, kind)
+        J, _ = Cs.misfit(tt, picks[vol_e], None if w is None else w[vol_e])
+        assert np.array_equal(u64(res.volumes.cpu().numpy()[0]), u64(J)), "the volume of an event of the last batch"
+        del res
+        for lo, hi in [(s - 5, s + 6) for s in starts[1:]] + [(eb - 1, eb), (eb, eb + 1), (E - 7, E)]:
+            s = sol.locate(tdev, pd[lo:hi], None if wd is None else wd[lo:hi])
+            sc, sm, st = outputs(s)
+            assert np.array_equal(sc, cell[lo:hi]), (variant, lo, hi)
+            assert np.array_equal(u64(sm), u64(mis[lo:hi])) and np.array_equal(u64(st), u64(t0[lo:hi])), (lo, hi)
+
+
+def test_more_events_than_one_launch_takes(P):
+    """2 x 3 x 2 cells, K = 2, 65535 * 8 + 3 events that repeat 97 distinct rows: the last three events are a second
+    batch.  The distinct rows against the restatement, every event against its row, four volumes around the edge."""
+    import torch
+    tt, rows_p, rows_w, _ = Cs.cap_case()
+    E = Cs.CAP_E
+    assert Cs.batches(Cs.CAP_SHAPE, E)[2] == [0, E - 3]
+    picks, w = Cs.periodic(rows_p, E), Cs.periodic(rows_w, E)
+    vols = [0, Cs.CAP - 1, Cs.CAP, E - 1]
+    with P.TravelTimeSolver(Cs.CAP_SHAPE, star818(P)) as sol:
+        res = sol.locate(torch.from_numpy(tt).to(dev()), picks, w, misfit_events=vols)
+    cell, mis, t0 = outputs(res)
+    rc, rm, rt, _ = Cs.locate_rows(tt, rows_p, rows_w)
+    assert np.all(rc >= 0) and np.array_equal(cell[:Cs.CAP_P], rc)
+    assert np.array_equal(u64(mis[:Cs.CAP_P]), u64(rm)) and np.array_equal(u64(t0[:Cs.CAP_P]), u64(rt))
+    assert_periodic(cell, mis, t0, Cs.CAP_P, "cap")
+    got = res.volumes.cpu().numpy()
+    for v, e in enumerate(vols):
+        assert np.array_equal(u64(got[v]), u64(Cs.misfit(tt, picks[e], w[e])[0])), e
+
+
+@pytest.mark.parametrize("N", sorted(Cs.N_SHAPES))
+def test_full_and_just_over_full_register_widths(P, N):
+    """K in 1, 2, 7 ... 33 around every register instance of loc_kr() on a grid of N cells (around the 256-cell
+    volume block and the 4096-cell tile): ten weighted events (dense, +0 at k = 0, +0 at k = K-1, -0.0 at a station
+    whose box is partly at infinity, one station picked) and three with weights NULL, every volume."""
+    with P.TravelTimeSolver(Cs.N_SHAPES[N], star818(P)) as sol:
+        for K in Cs.K_EDGES:
+            c = Cs.k_edge_case(K, N)
+            check_locate(P, c["tt"], c["picks"], c["weights"], vol_events=tuple(range(Cs.K_E)), what=f"K={K} N={N}",
+                         sol=sol)
+            check_locate(P, c["tt"], c["none"]["picks"], None, vol_events=tuple(range(Cs.K_E_NONE)),
+                         what=f"K={K} N={N}, weights NULL", sol=sol)
+
+
+@pytest.mark.parametrize("route", Cs.RANGE_ROUTES)
+def test_double_range_of_picks_and_weights(P, route):
+    """Picks and weights at the ends of the double range (overflow of S1 and of (w r) r, INF - INF, W = INF with
+    invW = 0, 1 / W = INF, subnormal weights and residuals): accepted, and the same bits as the restatement."""
+    tt, picks, w = Cs.range_case(route)
+    assert L.check(picks, w) is None
+    res = check_locate(P, tt, picks, w, vol_events=tuple(range(len(picks))), what=route)
+    cell, mis, t0 = outputs(res)
+    assert np.all((cell >= 0) == (mis < np.inf)) and np.all(np.isnan(t0) == (cell < 0))

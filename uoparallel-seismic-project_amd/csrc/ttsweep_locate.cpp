@@ -18,6 +18,7 @@ namespace {
 size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // per-tile partials of one batch of events, at most (12 bytes each)
+// (mirrored: tests/test_locate_cpu.py::test_case_constants_mirror_the_sources)
 constexpr long long LOC_PARTIALS = 1LL << 24;
 
 struct DevScratch {

@@ -26,7 +26,7 @@
 namespace ttsweep {
 
 constexpr int LOC_BLOCK = 256;
-constexpr int LOC_ET = 8;       // events per search block
+constexpr int LOC_ET = 8;       // events per search block (mirrored: tests/test_locate_cpu.py::test_case_constants_mirror_the_sources)
 constexpr int LOC_C = 16;       // cells per lane per search block: a tile is LOC_C * LOC_BLOCK cells
 constexpr unsigned long long LOC_INF = 0x7ff0000000000000ULL;
 
