@@ -411,6 +411,32 @@ int ttsweep_locate_device(ttsweep_ctx *ctx, int nbox, const float *const *tt_dev
                           int *cell_dev, double *misfit_dev, double *t0_dev,
                           int nvol, const int *vol_events, double *const *vol_dev);
 
+/* ---- locate window: the search of "locate" over a window and a lattice per event ---- */
+/* J(x), t0(x) and admissibility are exactly those of "locate" above: the same operations in the same order, so the
+ * same bits.  The candidate set of event e is
+ *   C(e) = { (x,y,z) : lo[e][a] <= coord_a <= hi[e][a]  and  (coord_a - lo[e][a]) % stride[a] == 0, each axis a }
+ * an axis-aligned window, inclusive, with a lattice anchored at the window's own lo.  Per event:
+ *   cell[e]   the smallest FLOATBOX index among the admissible cells of C(e) of minimal J, -1 when there is none
+ *   misfit[e] J(cell[e]), +INFINITY when there is none
+ *   t0[e]     t0(cell[e]), the quiet NaN of ttsweep_locate_device when there is none
+ * With the whole grid and stride 1 these are the outputs of ttsweep_locate_device.  Bit-identical from call to call,
+ * whatever the launch, the batch, which events share the call or how their windows repeat (consecutive events with
+ * one window share the loads of a cell's travel times; that decides the traffic only).
+ *   lo, hi          : host, int32 [nevent][3], inclusive; both NULL: the whole grid for every event
+ *   stride          : host, int32 [3], each >= 1; NULL: 1, 1, 1.  A stride beyond the window leaves the node at lo
+ *   tt_dev, picks_dev, weights_dev, cell_dev, misfit_dev, t0_dev : as for ttsweep_locate_device; each output may be NULL
+ * The call allocates nothing that grows with the grid: its scratch follows the events and the candidates of a batch
+ * of events, and the batches are cut under a fixed budget.
+ * Refused, before any output is touched: everything ttsweep_locate_device refuses for its arguments, picks and
+ * weights; lo without hi or hi without lo; lo[e][a] < 0, hi[e][a] >= n_a or lo[e][a] > hi[e][a] (the message names
+ * the event); a stride below 1.  The boxes and the context's state are left as they are (a following ttsweep_solve
+ * of the same boxes is still answered as a confirming pass).  Returns 0, or < 0 with ttsweep_last_error set. */
+#define TTSWEEP_HAS_LOCATE_WINDOW 1 /* the call below exists (TTSWEEP_ABI_VERSION stays 6) */
+int ttsweep_locate_window_device(ttsweep_ctx *ctx, int nbox, const float *const *tt_dev,
+                                 int nevent, const double *picks_dev, const double *weights_dev,
+                                 const int *lo, const int *hi, const int *stride,
+                                 int *cell_dev, double *misfit_dev, double *t0_dev);
+
 /* ---- locate confidence: confidence regions of located events, without misfit volumes ---- */
 /* J(x), t0(x) and admissibility are exactly those of "locate" above: the same operations in the same order, so the
  * same bits.  Per event e a reference level m[e] (normally misfit[e] of ttsweep_locate_device) and nlevel thresholds

@@ -196,6 +196,35 @@ hipError_t launch_locate_final(const float *const *boxes, int K, const double *p
 hipError_t launch_locate_volume(const float *const *boxes, int K, int N, const double *picks, const double *weights,
                                 const double *invw, const int *vev, double *const *vol, int nvol, hipStream_t st);
 
+// windowed, strided event location (ttsweep_locate.hip).  A group is up to 8 consecutive events that share one
+// window: its candidates q = (cx * cy_n + cy) * cz_n + cz (z fastest, ncand of them) are the cells of FLOATBOX
+// index x0 + cx * mx + cy * my + cz * mz (x0 the window's lo corner; mx, my, mz = sx * ny * nz, sy * nz, sz the index
+// steps of the lattice), cut into ntiles tiles of locate_window_tile_cells().  The
+// partials of its event i are [part + i * ntiles + tile].  search: one block per entry of the block table; final: cell
+// / misfit / t0 (each may be nullptr) of events e0 .. e0 + ne - 1 from the ev_ntiles[e - e0] partials at
+// ev_part[e - e0]
+constexpr int LOC_WIN_ET = 8;       // events of a group, at most
+struct WinGroup {
+    int e0, ne;             // first event and number of events
+    int x0;                 // FLOATBOX index of the window's lo corner
+    int cy, cz;             // lattice nodes along y and z
+    int ncand, ntiles;
+    long long part;
+};
+struct WinBlock {
+    int group, tile;
+};
+int locate_window_tile_cells();
+hipError_t launch_locate_window_search(const float *const *boxes, int K, int mx, int my, int mz,
+                                       const double *picks, const double *weights, const double *invw,
+                                       const WinGroup *groups, const WinBlock *blocks, int nblocks,
+                                       unsigned long long *part_key, int *part_x, hipStream_t st);
+hipError_t launch_locate_window_final(const float *const *boxes, int K, const double *picks, const double *weights,
+                                      const double *invw, int e0, int ne, const long long *ev_part,
+                                      const int *ev_ntiles, const unsigned long long *part_key, const int *part_x,
+                                      int *cell, double *misfit, double *t0, unsigned long long nan_bits,
+                                      hipStream_t st);
+
 // confidence regions of located events (ttsweep_locate.hip).  check: lim[e * L + l], the exclusive limit on the bits
 // of J of level l (0: the empty region), limmax[e] their greatest, flag[e] (bit 0 a NaN or negative m, bit 1 a NaN or
 // negative delta); init: the n = nevent * L accumulators (g_sum [n][10], g_t0 [n][2] keys, g_box [n][6]) at their

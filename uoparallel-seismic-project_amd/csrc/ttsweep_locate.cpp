@@ -1,5 +1,5 @@
-// ttsweep_locate.cpp - ttsweep_locate_device and ttsweep_locate_confidence_device of include/ttsweep.h (kernels:
-// ttsweep_locate.hip).  For locate: argument
+// ttsweep_locate.cpp - ttsweep_locate_device, ttsweep_locate_window_device and ttsweep_locate_confidence_device of
+// include/ttsweep.h (kernels: ttsweep_locate.hip).  For locate: argument
 // checks, the check scan of picks and weights (refused before any output is touched), event batches sized so that
 // the per-tile partials stay within a fixed scratch budget, the misfit volumes.  The scratch is allocated per call:
 // nothing of the context changes, so the boxes the confirming-pass shortcut of ttsweep_solve remembers, its pools
@@ -20,6 +20,9 @@ size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
 // per-tile partials of one batch of events, at most (12 bytes each)
 // (mirrored: tests/test_locate_cpu.py::test_case_constants_mirror_the_sources)
 constexpr long long LOC_PARTIALS = 1LL << 24;
+
+// blocks (group, tile) of one batch of ttsweep_locate_window_device, at most (8 bytes each)
+constexpr long long LOC_WIN_BLOCKS = 1LL << 22;
 
 struct DevScratch {
     char *p = nullptr;
@@ -98,6 +101,167 @@ int ttsweep_locate_device(ttsweep_ctx *ctx, int nbox, const float *const *tt_dev
         HIPCHK(launch_locate_volume(d_boxes, nbox, N, picks_dev, weights_dev, d_invw, d_vev, d_vol, nvol, ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// Windows and strides are host arrays, so every refusal that concerns them comes before the device is touched.  The
+// events are cut into groups of at most 8 consecutive events with one window (the kernel loads a candidate's travel
+// times once per group), the groups into batches whose partials stay within LOC_PARTIALS and whose block table within
+// LOC_WIN_BLOCKS entries.  The scratch is 28 bytes per event, 40 per group, 8 per block and 12 per partial of the
+// largest batch: nothing grows with the grid.
+int ttsweep_locate_window_device(ttsweep_ctx *ctx, int nbox, const float *const *tt_dev, int nevent,
+                                 const double *picks_dev, const double *weights_dev, const int *lo, const int *hi,
+                                 const int *stride, int *cell_dev, double *misfit_dev, double *t0_dev)
+{
+    const char *what = "ttsweep_locate_window_device";
+    if (nbox < 1 || nevent < 1 || !tt_dev || !picks_dev) return set_error("%s: null or bad argument", what);
+    if ((long long)nbox * nevent > INT_MAX)
+        return set_error("%s: %d boxes x %d events do not fit int32 pick indices", what, nbox, nevent);
+    if (!lo != !hi) return set_error("%s: lo and hi must both be given or both be NULL", what);
+    int st[3] = {1, 1, 1};
+    for (int a = 0; stride && a < 3; a++) {
+        if (stride[a] < 1) return set_error("%s: stride %d along axis %d is below 1", what, stride[a], a);
+        st[a] = stride[a];
+    }
+    for (long long i = 0; lo && i < 3LL * nevent; i++)
+        if (lo[i] < 0 || lo[i] > hi[i])
+            return set_error("%s: event %d has a bad window [%d, %d] along axis %d", what, (int)(i / 3), lo[i], hi[i],
+                             (int)(i % 3));
+    if (!ctx) return set_error("%s: null or bad argument", what);
+    const long long ncells = (long long)ctx->nx * ctx->ny * ctx->nz;
+    if (ncells > INT_MAX)
+        return set_error("%s: %d x %d x %d cells do not fit int32 indices", what, ctx->nx, ctx->ny, ctx->nz);
+    const int n[3] = {ctx->nx, ctx->ny, ctx->nz};
+    for (long long i = 0; hi && i < 3LL * nevent; i++)
+        if (hi[i] >= n[i % 3])
+            return set_error("%s: event %d has a window [%d, %d] along axis %d that leaves the grid (%d cells)", what,
+                             (int)(i / 3), lo[i], hi[i], (int)(i % 3), n[i % 3]);
+    for (int k = 0; k < nbox; k++)
+        if (!tt_dev[k]) return set_error("%s: null box pointer %d", what, k);
+
+    // groups, and batches of groups [first group, end group) with their partials, blocks and events
+    const int whole_lo[3] = {0, 0, 0}, whole_hi[3] = {n[0] - 1, n[1] - 1, n[2] - 1};
+    auto win_lo = [&](int e) { return lo ? lo + 3LL * e : whole_lo; };
+    auto win_hi = [&](int e) { return hi ? hi + 3LL * e : whole_hi; };
+    const int tile = locate_window_tile_cells();
+    // the index steps of the lattice; a stride beyond the grid is never stepped (one node along that axis)
+    const int mx = (int)std::min<long long>(st[0], n[0]) * n[1] * n[2], my = (int)std::min<long long>(st[1], n[1]) * n[2];
+    const int mz = std::min(st[2], n[2]);
+    std::vector<WinGroup> groups;
+    for (int e = 0; e < nevent;) {
+        const int *l = win_lo(e), *h = win_hi(e);
+        int ne = 1;
+        while (ne < LOC_WIN_ET && e + ne < nevent && !memcmp(win_lo(e + ne), l, 3 * sizeof(int)) &&
+               !memcmp(win_hi(e + ne), h, 3 * sizeof(int)))
+            ne++;
+        WinGroup g;
+        g.e0 = e;
+        g.ne = ne;
+        long long c[3];
+        for (int a = 0; a < 3; a++) c[a] = (h[a] - l[a]) / st[a] + 1;
+        g.x0 = (l[0] * n[1] + l[1]) * n[2] + l[2];
+        g.cy = (int)c[1];
+        g.cz = (int)c[2];
+        g.ncand = (int)(c[0] * c[1] * c[2]);            // at most ncells
+        g.ntiles = (g.ncand + tile - 1) / tile;
+        g.part = 0;
+        groups.push_back(g);
+        e += ne;
+    }
+    struct Batch {
+        size_t g0, g1;
+        long long parts, blocks;
+    };
+    std::vector<Batch> batches;
+    long long maxp = 1, maxb = 1;
+    size_t maxg = 1;
+    int maxe = 1;
+    for (size_t g = 0; g < groups.size();) {
+        Batch b{g, g, 0, 0};
+        while (b.g1 < groups.size()) {
+            const WinGroup &G = groups[b.g1];
+            if (b.g1 > b.g0 && (b.parts + (long long)G.ne * G.ntiles > LOC_PARTIALS || b.blocks + G.ntiles > LOC_WIN_BLOCKS))
+                break;
+            b.parts += (long long)G.ne * G.ntiles;
+            b.blocks += G.ntiles;
+            b.g1++;
+        }
+        batches.push_back(b);
+        maxp = std::max(maxp, b.parts);
+        maxb = std::max(maxb, b.blocks);
+        maxg = std::max(maxg, b.g1 - b.g0);
+        maxe = std::max(maxe, groups[b.g1 - 1].e0 + groups[b.g1 - 1].ne - groups[b.g0].e0);
+        g = b.g1;
+    }
+    if (ctx_bind(ctx)) return -1;
+
+    const size_t bb = align_up(nbox * sizeof(float *)), bi = align_up(nevent * sizeof(double));
+    const size_t bf = align_up(nevent * sizeof(int)), bg = align_up(maxg * sizeof(WinGroup));
+    const size_t bl = align_up((size_t)maxb * sizeof(WinBlock)), bo = align_up((size_t)maxe * sizeof(long long));
+    const size_t bn = align_up((size_t)maxe * sizeof(int));
+    const size_t bk = align_up((size_t)maxp * sizeof(unsigned long long)), bx = align_up((size_t)maxp * sizeof(int));
+    DevScratch S;
+    HIPCHK(hipMalloc((void **)&S.p, bb + bi + bf + bg + bl + bo + bn + bk + bx));
+    char *p = S.p;
+    auto take = [&p](size_t bytes) {
+        char *q = p;
+        p += bytes;
+        return q;
+    };
+    const float **d_boxes = (const float **)take(bb);
+    double *d_invw = (double *)take(bi);
+    int *d_flag = (int *)take(bf);
+    WinGroup *d_groups = (WinGroup *)take(bg);
+    WinBlock *d_blocks = (WinBlock *)take(bl);
+    long long *d_evpart = (long long *)take(bo);
+    int *d_evnt = (int *)take(bn);
+    unsigned long long *d_key = (unsigned long long *)take(bk);
+    int *d_x = (int *)take(bx);
+
+    HIPCHK(hipMemcpyAsync(d_boxes, tt_dev, nbox * sizeof(float *), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(launch_locate_check(nbox, nevent, picks_dev, weights_dev, d_invw, d_flag, ctx->stream));
+    std::vector<int> flag(nevent);
+    HIPCHK(hipMemcpyAsync(flag.data(), d_flag, nevent * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int e = 0; e < nevent; e++) {
+        if (flag[e] & 1) return set_error("%s: event %d has a NaN or infinite pick", what, e);
+        if (flag[e] & 2) return set_error("%s: event %d has a negative, NaN or infinite weight", what, e);
+        if (flag[e] & 4) return set_error("%s: event %d has no weight above zero", what, e);
+    }
+    if (!cell_dev && !misfit_dev && !t0_dev) return 0;
+
+    const unsigned long long nan_bits = 0x7ff8000000000000ULL;     // as ttsweep_locate_device
+    std::vector<WinBlock> blocks;
+    std::vector<long long> evpart;
+    std::vector<int> evnt;
+    for (const Batch &b : batches) {
+        blocks.clear();
+        evpart.clear();
+        evnt.clear();
+        long long part = 0;
+        for (size_t g = b.g0; g < b.g1; g++) {
+            WinGroup &G = groups[g];
+            G.part = part;
+            for (int i = 0; i < G.ne; i++) {
+                evpart.push_back(part + (long long)i * G.ntiles);
+                evnt.push_back(G.ntiles);
+            }
+            part += (long long)G.ne * G.ntiles;
+            for (int t = 0; t < G.ntiles; t++) blocks.push_back(WinBlock{(int)(g - b.g0), t});
+        }
+        const int e0 = groups[b.g0].e0, ne = (int)evnt.size();
+        HIPCHK(hipMemcpyAsync(d_groups, groups.data() + b.g0, (b.g1 - b.g0) * sizeof(WinGroup), hipMemcpyHostToDevice,
+                              ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_blocks, blocks.data(), blocks.size() * sizeof(WinBlock), hipMemcpyHostToDevice,
+                              ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_evpart, evpart.data(), ne * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_evnt, evnt.data(), ne * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(launch_locate_window_search(d_boxes, nbox, mx, my, mz, picks_dev, weights_dev,
+                                           d_invw, d_groups, d_blocks, (int)blocks.size(), d_key, d_x, ctx->stream));
+        HIPCHK(launch_locate_window_final(d_boxes, nbox, picks_dev, weights_dev, d_invw, e0, ne, d_evpart, d_evnt,
+                                          d_key, d_x, cell_dev, misfit_dev, t0_dev, nan_bits, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));      // the host tables are rebuilt for the next batch
+    }
     return 0;
 }
 

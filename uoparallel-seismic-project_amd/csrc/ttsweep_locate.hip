@@ -13,6 +13,7 @@
 //                           reduction per event and tile gives a per-tile partial (J bits, x)
 //   locate_final_kernel     one block per event: the smallest (J bits, x) over the tiles, then t0 at that cell
 //   locate_volume_kernel    J (+INF where inadmissible) of every cell for a list of events
+//   locate_window_*_kernel  the same search over a window and lattice per event ("locate window", further down)
 // A cell is inadmissible when a picked station has T >= +INFINITY or J is not below +INFINITY.  The first implies
 // the second in IEEE arithmetic (o - INF = -INF enters S1, so t0 is -INF or NaN and r of that station is NaN), so
 // one test on the bits of J covers both: J >= 0 always, and +INF and every NaN compare above it as unsigned
@@ -268,6 +269,142 @@ locate_volume_kernel(const float *const *__restrict__ boxes, int K, int N, const
     }
     const unsigned long long key = dbits(J);
     vol[blockIdx.y][x] = key < LOC_INF ? key : LOC_INF;
+}
+
+// ---- windowed, strided search (include/ttsweep.h, "locate window") ----
+// The candidates of an event are the nodes of a lattice inside its window.  The host cuts the events into groups of at
+// most LOC_ET consecutive events with one window (WinGroup) and lists every (group, tile of LOC_WC * LOC_BLOCK
+// candidates) as a block (WinBlock).  A lane decodes its candidate number q (z fastest) to a cell once per step, with
+// two divisions, loads the K travel times of that cell once and scores the events of the group on them: the cell
+// loop, event loop, loc_misfit and the per-lane minimum in LDS of locate_search_kernel.  The cell index ascends with
+// q, so the strict compare of a lane and the lexicographic minimum of (bits of J, cell) give the smallest index among
+// the candidates of minimal J whatever the grouping.
+//   locate_window_search_kernel  one block per WinBlock; the partial of event i of the group at
+//                                [group.part + i * group.ntiles + tile]
+//   locate_window_final_kernel   one block per event: the smallest of its partials, then t0 at that cell
+constexpr int LOC_WC = 16;      // candidates per lane per window block
+static_assert(LOC_WIN_ET <= LOC_ET, "a group's events share the per-lane minima of one block");
+
+template <int KR>
+__global__ void __launch_bounds__(LOC_BLOCK)
+locate_window_search_kernel(const float *const *__restrict__ boxes, int K, int mx, int my, int mz,
+                            const double *__restrict__ picks, const double *__restrict__ weights,
+                            const double *__restrict__ invw, const WinGroup *__restrict__ groups,
+                            const WinBlock *__restrict__ blocks, unsigned long long *__restrict__ part_key,
+                            int *__restrict__ part_x)
+{
+    __shared__ unsigned long long s_key[LOC_ET][LOC_BLOCK];
+    __shared__ int s_x[LOC_ET][LOC_BLOCK];
+    const int tid = threadIdx.x;
+    const WinBlock B = blocks[blockIdx.x];              // uniform: scalar loads
+    const WinGroup G = groups[B.group];
+    const int net = G.ne;
+#pragma unroll
+    for (int i = 0; i < LOC_ET; i++) {
+        s_key[i][tid] = LOC_INF;
+        s_x[i][tid] = 0x7fffffff;
+    }
+    // uniform loops as in locate_search_kernel: lanes past the last candidate compute it again and keep nothing
+    const long long base = (long long)B.tile * (LOC_WC * LOC_BLOCK);
+    const int nj = (int)min((long long)LOC_WC, (G.ncand - base + LOC_BLOCK - 1) / LOC_BLOCK);
+    for (int j = 0; j < nj; j++) {
+        const long long ql = base + (long long)j * LOC_BLOCK + tid;
+        const bool in = ql < G.ncand;
+        const unsigned q = in ? (unsigned)ql : (unsigned)(G.ncand - 1);
+        const unsigned qxy = q / (unsigned)G.cz, cz = q - qxy * (unsigned)G.cz;
+        const unsigned cx = qxy / (unsigned)G.cy, cy = qxy - cx * (unsigned)G.cy;
+        const int x = G.x0 + (int)cx * mx + (int)cy * my + (int)cz * mz;
+        double tr[KR > 0 ? KR : 1];
+        if constexpr (KR > 0) {
+#pragma unroll
+            for (int k = 0; k < KR; k++) tr[k] = k < K ? (double)boxes[k][x] : 0.0;
+        }
+        for (int i = 0; i < net; i++) {
+            const int e = __builtin_amdgcn_readfirstlane(G.e0 + i);
+            const double *o = picks + (long long)e * K;
+            const double *w = weights ? weights + (long long)e * K : nullptr;
+            double t0;
+            const double J = KR > 0 ? loc_misfit<KR>([&](int k) { return tr[k]; }, K, o, w, invw[e], t0)
+                                    : loc_misfit<0>([&](int k) { return (double)boxes[k][x]; }, K, o, w, invw[e], t0);
+            const unsigned long long key = dbits(J);
+            if (in && key < s_key[i][tid]) {     // cells of a lane ascend: strict keeps the smallest x
+                s_key[i][tid] = key;
+                s_x[i][tid] = x;
+            }
+        }
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int i = wave; i < net; i += LOC_BLOCK / 64) {
+        unsigned long long key = s_key[i][lane];
+        int x = s_x[i][lane];
+#pragma unroll
+        for (int q = 1; q < LOC_BLOCK / 64; q++) {
+            const unsigned long long k2 = s_key[i][lane + 64 * q];
+            const int x2 = s_x[i][lane + 64 * q];
+            if (loc_less(k2, x2, key, x)) {
+                key = k2;
+                x = x2;
+            }
+        }
+        loc_wave_min(key, x);
+        if (lane == 0) {
+            const long long p = G.part + (long long)i * G.ntiles + B.tile;
+            part_key[p] = key;
+            part_x[p] = x;
+        }
+    }
+}
+
+// one block per event e0 + blockIdx.x: the smallest (J bits, x) of its ev_ntiles partials from ev_part; the outputs
+// of locate_final_kernel
+__global__ void __launch_bounds__(LOC_BLOCK)
+locate_window_final_kernel(const float *const *__restrict__ boxes, int K, const double *__restrict__ picks,
+                           const double *__restrict__ weights, const double *__restrict__ invw, int e0,
+                           const long long *__restrict__ ev_part, const int *__restrict__ ev_ntiles,
+                           const unsigned long long *__restrict__ part_key, const int *__restrict__ part_x,
+                           int *__restrict__ cell, unsigned long long *__restrict__ misfit,
+                           unsigned long long *__restrict__ t0out, unsigned long long nan_bits)
+{
+    __shared__ unsigned long long s_key[LOC_BLOCK / 64];
+    __shared__ int s_x[LOC_BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int e = e0 + blockIdx.x;
+    const long long p0 = ev_part[blockIdx.x];
+    const int ntiles = ev_ntiles[blockIdx.x];
+    unsigned long long key = LOC_INF;
+    int x = 0x7fffffff;
+    for (int t = tid; t < ntiles; t += LOC_BLOCK)
+        if (loc_less(part_key[p0 + t], part_x[p0 + t], key, x)) {
+            key = part_key[p0 + t];
+            x = part_x[p0 + t];
+        }
+    loc_wave_min(key, x);
+    if (lane == 0) {
+        s_key[wave] = key;
+        s_x[wave] = x;
+    }
+    __syncthreads();
+    if (tid) return;
+    key = s_key[0];
+    x = s_x[0];
+    for (int q = 1; q < LOC_BLOCK / 64; q++)
+        if (loc_less(s_key[q], s_x[q], key, x)) {
+            key = s_key[q];
+            x = s_x[q];
+        }
+    const bool found = key < LOC_INF;
+    unsigned long long tb = nan_bits;
+    if (found) {
+        const double *o = picks + (long long)e * K;
+        const double *w = weights ? weights + (long long)e * K : nullptr;
+        double t0;
+        loc_misfit<0>([&](int k) { return (double)boxes[k][x]; }, K, o, w, invw[e], t0);
+        tb = dbits(t0);
+    }
+    if (cell) cell[e] = found ? x : -1;
+    if (misfit) misfit[e] = found ? key : LOC_INF;
+    if (t0out) t0out[e] = tb;
 }
 
 // ---- confidence regions (include/ttsweep.h, "locate confidence") ----
@@ -548,6 +685,43 @@ hipError_t launch_locate_volume(const float *const *boxes, int K, int N, const d
     default: hipLaunchKernelGGL(locate_volume_kernel<0>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, N, picks, weights,
                                 invw, vev, v); break;
     }
+    return hipGetLastError();
+}
+
+int locate_window_tile_cells() { return LOC_WC * LOC_BLOCK; }
+
+hipError_t launch_locate_window_search(const float *const *boxes, int K, int mx, int my, int mz,
+                                       const double *picks, const double *weights, const double *invw,
+                                       const WinGroup *groups, const WinBlock *blocks, int nblocks,
+                                       unsigned long long *part_key, int *part_x, hipStream_t st)
+{
+    if (nblocks <= 0) return hipSuccess;
+    const dim3 grid(nblocks);
+    switch (loc_kr(K)) {
+    case 8: hipLaunchKernelGGL(locate_window_search_kernel<8>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, mx, my, mz,
+                                picks, weights, invw, groups, blocks, part_key, part_x); break;
+    case 16: hipLaunchKernelGGL(locate_window_search_kernel<16>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, mx, my, mz,
+                                picks, weights, invw, groups, blocks, part_key, part_x); break;
+    case 24: hipLaunchKernelGGL(locate_window_search_kernel<24>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, mx, my, mz,
+                                picks, weights, invw, groups, blocks, part_key, part_x); break;
+    case 32: hipLaunchKernelGGL(locate_window_search_kernel<32>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, mx, my, mz,
+                                picks, weights, invw, groups, blocks, part_key, part_x); break;
+    default: hipLaunchKernelGGL(locate_window_search_kernel<0>, grid, dim3(LOC_BLOCK), 0, st, boxes, K, mx, my, mz,
+                                picks, weights, invw, groups, blocks, part_key, part_x); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_window_final(const float *const *boxes, int K, const double *picks, const double *weights,
+                                      const double *invw, int e0, int ne, const long long *ev_part,
+                                      const int *ev_ntiles, const unsigned long long *part_key, const int *part_x,
+                                      int *cell, double *misfit, double *t0, unsigned long long nan_bits,
+                                      hipStream_t st)
+{
+    if (ne <= 0) return hipSuccess;
+    hipLaunchKernelGGL(locate_window_final_kernel, dim3(ne), dim3(LOC_BLOCK), 0, st, boxes, K, picks, weights, invw, e0,
+                       ev_part, ev_ntiles, part_key, part_x, cell, (unsigned long long *)misfit,
+                       (unsigned long long *)t0, nan_bits);
     return hipGetLastError();
 }
 

@@ -241,6 +241,26 @@ class TravelTimeSolver:
         [E,K] float64 torch tensors on that device, or numpy arrays (copied over); weights None: every weight 1.0,
         a zero weight: no pick.  misfit_events: event indices whose misfit volume J is returned as well."""
         import torch
+        K, E, dev, picks, weights = self._locate_inputs(tt, picks, weights)
+        vev = [] if misfit_events is None else [int(e) for e in misfit_events]
+        _require(all(0 <= e < E for e in vev), f"misfit_events: indices in [0, {E})")
+        cell = torch.empty(E, dtype=torch.int32, device=dev)
+        misfit = torch.empty(E, dtype=torch.float64, device=dev)
+        t0 = torch.empty(E, dtype=torch.float64, device=dev)
+        vols = torch.empty((len(vev),) + self.shape, dtype=torch.float64, device=dev) if vev else None
+        varr = (C.c_int * max(len(vev), 1))(*vev)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.ttsweep_locate_device(
+            self._ctx, K, self._box_pointers(tt, K), E, picks.data_ptr(),
+            None if weights is None else weights.data_ptr(), cell.data_ptr(), misfit.data_ptr(), t0.data_ptr(),
+            len(vev), varr if vev else None, self._box_pointers(vols, len(vev)) if vev else None),
+            "ttsweep_locate_device")
+        return Locations(cell, self._cell_xyz(cell), misfit, t0, vols)
+
+    def _locate_inputs(self, tt, picks, weights):
+        """(K, E, device, picks, weights) of a locate call, checked: tt [K,nx,ny,nz] float32 on this solver's device,
+        picks / weights [E,K] float64 contiguous on it (numpy arrays are copied over; weights may be None)."""
+        import torch
         _require(isinstance(tt, torch.Tensor) and tt.dim() == 4, "tt: torch float32 [K, nx, ny, nz]")
         K = int(tt.shape[0])
         self._require_device_tensor(tt, (K,) + self.shape, "station boxes")
@@ -260,24 +280,75 @@ class TravelTimeSolver:
         if weights is not None:
             weights = events_by_stations(weights, "weights")
             _require(tuple(weights.shape) == (E, K), f"weights: shape {tuple(weights.shape)}, want {(E, K)}")
-        vev = [] if misfit_events is None else [int(e) for e in misfit_events]
-        _require(all(0 <= e < E for e in vev), f"misfit_events: indices in [0, {E})")
-        cell = torch.empty(E, dtype=torch.int32, device=dev)
-        misfit = torch.empty(E, dtype=torch.float64, device=dev)
-        t0 = torch.empty(E, dtype=torch.float64, device=dev)
-        vols = torch.empty((len(vev),) + self.shape, dtype=torch.float64, device=dev) if vev else None
-        varr = (C.c_int * max(len(vev), 1))(*vev)
-        torch.cuda.current_stream(dev).synchronize()
-        _check(self._L.ttsweep_locate_device(
-            self._ctx, K, self._box_pointers(tt, K), E, picks.data_ptr(),
-            None if weights is None else weights.data_ptr(), cell.data_ptr(), misfit.data_ptr(), t0.data_ptr(),
-            len(vev), varr if vev else None, self._box_pointers(vols, len(vev)) if vev else None),
-            "ttsweep_locate_device")
+        return K, E, dev, picks, weights
+
+    def _cell_xyz(self, cell):
+        """[E,3] int32 on the host: the FLOATBOX indices as (x, y, z), (-1, -1, -1) for -1."""
+        import torch
         c = cell.cpu().to(torch.int64)
         nyz = self.shape[1] * self.shape[2]
         xyz = torch.stack([c // nyz, (c // self.shape[2]) % self.shape[1], c % self.shape[2]], dim=1).to(torch.int32)
         xyz[c < 0] = -1
-        return Locations(cell, xyz, misfit, t0, vols)
+        return xyz
+
+    def locate_window(self, tt, picks, weights=None, lo=None, hi=None, stride=1) -> "Locations":
+        """ttsweep_locate_window_device: the search of locate over a window and a lattice per event (include/ttsweep.h,
+        "locate window").  tt, picks, weights as for locate.  lo, hi: the inclusive window as [3] (every event) or
+        [E,3] integers, numpy or lists; both None: the whole grid.  stride: an int or [3], >= 1; the lattice is
+        anchored at the window's lo.  The candidates of event e are the cells lo[e] + i * stride <= hi[e]; cell is
+        the smallest index among those of minimal J.  volumes is None in the result."""
+        import torch
+        K, E, dev, picks, weights = self._locate_inputs(tt, picks, weights)
+        _require((lo is None) == (hi is None), "lo and hi: both or neither")
+
+        def window(a, what):
+            if a is None:
+                return None
+            a = np.asarray(a)
+            _require(a.dtype.kind in "iu" and a.shape in ((3,), (E, 3)), f"{what}: integers, [3] or [{E}, 3]")
+            _require(a.size == 0 or (a.min() >= -2**31 and a.max() < 2**31), f"{what}: int32 values")
+            return np.ascontiguousarray(np.broadcast_to(a, (E, 3)), dtype=np.int32)
+
+        lo, hi = window(lo, "lo"), window(hi, "hi")
+        stride = np.asarray(stride)
+        _require(stride.dtype.kind in "iu" and stride.shape in ((), (3,)), "stride: an int or [3] integers")
+        _require(stride.min() >= -2**31 and stride.max() < 2**31, "stride: int32 values")
+        stride = np.ascontiguousarray(np.broadcast_to(stride, (3,)), dtype=np.int32)
+        cell = torch.empty(E, dtype=torch.int32, device=dev)
+        misfit = torch.empty(E, dtype=torch.float64, device=dev)
+        t0 = torch.empty(E, dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.ttsweep_locate_window_device(
+            self._ctx, K, self._box_pointers(tt, K), E, picks.data_ptr(),
+            None if weights is None else weights.data_ptr(), None if lo is None else lo.ctypes.data,
+            None if hi is None else hi.ctypes.data, stride.ctypes.data, cell.data_ptr(), misfit.data_ptr(),
+            t0.data_ptr()), "ttsweep_locate_window_device")
+        return Locations(cell, self._cell_xyz(cell), misfit, t0, None)
+
+    def locate_refine(self, tt, picks, weights=None, stride=4, radius=None) -> "Locations":
+        """Coarse-to-fine location in two calls of locate_window.  Stage 1 searches the whole grid on the lattice of
+        `stride` (an int or [3]) anchored at cell (0, 0, 0).  Stage 2 searches with stride 1, in one call for all
+        events: the window xyz +- radius around the stage-1 cell, clipped to the grid, for an event stage 1 placed;
+        the whole grid (which is exact) for an event whose lattice nodes are all inadmissible.  radius: an int or
+        [3], default the stride per axis, so that the cells past the last lattice node are covered.
+
+        NOT exact: the refined cell is locate's global minimum only where the basin of the misfit's minimum holds
+        the window of a lattice node, i.e. where the best lattice node lies within `radius` of the best cell.  By
+        construction misfit <= coarse_misfit (the lattice node is inside its window) and misfit >= locate's misfit.
+        The result carries the stage-2 outputs, and coarse_cell / coarse_misfit of stage 1."""
+        n = np.asarray(self.shape, dtype=np.int64)
+        stride = np.broadcast_to(np.asarray(stride), (3,))
+        radius = stride if radius is None else np.broadcast_to(np.asarray(radius), (3,))
+        _require(radius.dtype.kind in "iu" and radius.min() >= 0, "radius: a non-negative int or [3] integers")
+        _, _, _, picks, weights = self._locate_inputs(tt, picks, weights)       # copied to the device once
+        coarse = self.locate_window(tt, picks, weights, lo=np.zeros(3, np.int64), hi=n - 1, stride=stride)
+        xyz = coarse.xyz.numpy().astype(np.int64)
+        placed = (xyz[:, 0] >= 0)[:, None]
+        lo = np.where(placed, np.maximum(xyz - radius, 0), 0)
+        hi = np.where(placed, np.minimum(xyz + radius, n - 1), n - 1)
+        fine = self.locate_window(tt, picks, weights, lo=lo, hi=hi, stride=1)
+        fine.coarse_cell, fine.coarse_misfit = coarse.cell, coarse.misfit
+        return fine
 
     def locate_confidence(self, tt, picks, weights, misfit, delta) -> "ConfidenceRegions":
         """ttsweep_locate_confidence_device: per event and level the region of admissible cells with
@@ -362,12 +433,16 @@ class Locations:
       xyz     [E,3] int32 (host): the cell as (x, y, z), (-1, -1, -1) when there is none
       misfit  [E] float64 (device): the weighted L2 misfit J at the cell, +inf when there is none
       t0      [E] float64 (device): the origin time at the cell, NaN when there is none
-      volumes [nvol,nx,ny,nz] float64 (device) or None: J of every cell for misfit_events, +inf where inadmissible"""
+      volumes [nvol,nx,ny,nz] float64 (device) or None: J of every cell for misfit_events, +inf where inadmissible
+    locate_window fills the same fields over its candidates (volumes None); locate_refine adds
+      coarse_cell, coarse_misfit [E] int32 / float64 (device): cell and misfit of its stage 1 on the lattice"""
     cell: "object"
     xyz: "object"
     misfit: "object"
     t0: "object"
     volumes: "object"
+    coarse_cell: "object" = None
+    coarse_misfit: "object" = None
 
     def __len__(self):
         return len(self.cell)
