@@ -437,6 +437,49 @@ int ttsweep_locate_window_device(ttsweep_ctx *ctx, int nbox, const float *const 
                                  const int *lo, const int *hi, const int *stride,
                                  int *cell_dev, double *misfit_dev, double *t0_dev);
 
+/* ---- locate subcell: the search of "locate" over the nodes of a finer lattice, the boxes interpolated ---- */
+/* The candidates of event e are the nodes q = (qx, qy, qz) with lo[e][a] * sub <= q_a <= hi[e][a] * sub on each axis
+ * a: `sub` lattice steps per cell edge inside an inclusive window of cells.  Node q stands for the position q / sub,
+ * in cells.  Per axis of a node
+ *   i = q / sub (integer division)    f = q % sub    j = i + (f != 0)    u = (double)f / (double)sub
+ * j never leaves the window (f != 0 implies i < hi), so no cell outside [lo, hi] is read.  The time of station k at
+ * the node is interpolated trilinearly in double, every operation rounded on its own, no contraction, with
+ * lerp(a, b, u) = a + u * (b - a) (a subtraction, a multiplication, an addition) and T(x,y,z) = (double)T_k[(x*ny + y)*nz + z]:
+ *   c00 = lerp(T(ix,iy,iz), T(ix,iy,jz), uz)    c01 = lerp(T(ix,jy,iz), T(ix,jy,jz), uz)
+ *   c10 = lerp(T(jx,iy,iz), T(jx,iy,jz), uz)    c11 = lerp(T(jx,jy,iz), T(jx,jy,jz), uz)
+ *   c0  = lerp(c00, c01, uy)                    c1  = lerp(c10, c11, uy)            That_k(q) = lerp(c0, c1, ux)
+ * J(q) and t0(q) are the formulas of "locate" above with That_k(q) in place of (double)T_k[x]: the same station order,
+ * zero weights skipped, the same operations in the same order.  A node is admissible for e exactly when
+ * J(q) < +INFINITY.  A node is therefore inadmissible exactly when a picked station has a non-finite value at one of
+ * its eight corners (i|j): a non-finite corner always leaves That at +-INF or NaN, and then J is NaN.  Per event:
+ *   node[e]   the admissible node of minimal J, ties to the smallest (qx, qy, qz) in lexicographic order;
+ *             (-1, -1, -1) when there is none
+ *   misfit[e] J(node[e]), +INFINITY when there is none
+ *   t0[e]     t0(node[e]), the quiet NaN of ttsweep_locate_device when there is none
+ * 1. Where f = 0 on all three axes That_k is the cell's value (a + 0 * (a - a) is a; a float -0.0 becomes +0.0, which
+ *    changes no o - T), so J and t0 carry the bits "locate" gives that cell.
+ * 2. With sub = 1 the outputs are those of ttsweep_locate_window_device on the same window at stride 1, node being
+ *    that cell's (x, y, z).
+ * 3. For every sub, misfit[e] <= the misfit[e] of ttsweep_locate_window_device on the same window at stride 1.
+ * 4. Bit-identical from call to call, whatever the launch, the batch, which events share the call or how their windows
+ *    repeat (the nodes of a small window are scored from a copy of its cells in on-chip memory, those of a large one
+ *    from the boxes: the same values, the same operations).
+ *   lo, hi          : host, int32 [nevent][3], inclusive, in cells; both NULL: the whole grid for every event
+ *   sub             : lattice steps per cell edge, 1 <= sub <= 64
+ *   node_dev        : device, int32 [nevent][3]
+ *   tt_dev, picks_dev, weights_dev, misfit_dev, t0_dev : as for ttsweep_locate_window_device; each output may be NULL
+ * The call allocates nothing that grows with the grid: its scratch follows the events and the nodes of a batch of
+ * events, and the batches are cut under a fixed budget.
+ * Refused, before any output is touched: everything ttsweep_locate_window_device refuses for its arguments, picks,
+ * weights and windows; sub outside 1..64; (n_a - 1) * sub > INT32_MAX on an axis; an event with more than INT32_MAX
+ * nodes (the message names the event).  The boxes and the context's state are left as they are.  Returns 0, or < 0
+ * with ttsweep_last_error set. */
+#define TTSWEEP_HAS_LOCATE_SUBCELL 1 /* the call below exists (TTSWEEP_ABI_VERSION stays 6) */
+int ttsweep_locate_subcell_device(ttsweep_ctx *ctx, int nbox, const float *const *tt_dev,
+                                  int nevent, const double *picks_dev, const double *weights_dev,
+                                  const int *lo, const int *hi, int sub,
+                                  int *node_dev, double *misfit_dev, double *t0_dev);
+
 /* ---- locate confidence: confidence regions of located events, without misfit volumes ---- */
 /* J(x), t0(x) and admissibility are exactly those of "locate" above: the same operations in the same order, so the
  * same bits.  Per event e a reference level m[e] (normally misfit[e] of ttsweep_locate_device) and nlevel thresholds

@@ -225,6 +225,36 @@ hipError_t launch_locate_window_final(const float *const *boxes, int K, const do
                                       int *cell, double *misfit, double *t0, unsigned long long nan_bits,
                                       hipStream_t st);
 
+// sub-cell event location (ttsweep_locate.hip).  A group is up to 8 consecutive events that share one window of
+// wx * wy * wz = wn cells from the FLOATBOX index x0 (cell lo).  Its candidates are the nodes q = (qx * ny + qy) * nz
+// + qz (z fastest, relative to the window; nx, ny, nz = (w - 1) * sub + 1 nodes per axis, nnode of them), cut into
+// ntiles tiles of locate_subcell_tile_nodes().  staged: the K * wn floats of the window are at most
+// locate_subcell_stage_floats() and the blocks of the group copy them to LDS; such blocks and the others are listed
+// and launched apart.  The partials of its event i are [part + i * ntiles + tile].  search: one block per entry of the
+// block table; final: node [.][3] / misfit / t0 (each may be nullptr) of events e0 .. e0 + ne - 1, event e of group
+// ev_group[e - e0]
+struct SubGroup {
+    int e0, ne;             // first event and number of events
+    int x0;                 // FLOATBOX index of the window's lo corner
+    int lo[3];              // the window's lo corner, in cells
+    int wy, wz, wn;         // cells of the window along y and z, and in all
+    int ny, nz;             // nodes along y and z
+    int nnode, ntiles;
+    int staged;
+    long long part;
+};
+int locate_subcell_tile_nodes();
+int locate_subcell_stage_floats();
+hipError_t launch_locate_subcell_search(const float *const *boxes, int K, int gnyz, int gnz, int sub,
+                                        const double *picks, const double *weights, const double *invw,
+                                        const SubGroup *groups, const WinBlock *blocks, int nblocks, bool staged,
+                                        unsigned long long *part_key, int *part_x, hipStream_t st);
+hipError_t launch_locate_subcell_final(const float *const *boxes, int K, int gnyz, int gnz, int sub,
+                                       const double *picks, const double *weights, const double *invw, int e0, int ne,
+                                       const int *ev_group, const SubGroup *groups,
+                                       const unsigned long long *part_key, const int *part_x, int *node,
+                                       double *misfit, double *t0, unsigned long long nan_bits, hipStream_t st);
+
 // confidence regions of located events (ttsweep_locate.hip).  check: lim[e * L + l], the exclusive limit on the bits
 // of J of level l (0: the empty region), limmax[e] their greatest, flag[e] (bit 0 a NaN or negative m, bit 1 a NaN or
 // negative delta); init: the n = nevent * L accumulators (g_sum [n][10], g_t0 [n][2] keys, g_box [n][6]) at their

@@ -1,5 +1,5 @@
-// ttsweep_locate.cpp - ttsweep_locate_device, ttsweep_locate_window_device and ttsweep_locate_confidence_device of
-// include/ttsweep.h (kernels: ttsweep_locate.hip).  For locate: argument
+// ttsweep_locate.cpp - ttsweep_locate_device, ttsweep_locate_window_device, ttsweep_locate_subcell_device and
+// ttsweep_locate_confidence_device of include/ttsweep.h (kernels: ttsweep_locate.hip).  For locate: argument
 // checks, the check scan of picks and weights (refused before any output is touched), event batches sized so that
 // the per-tile partials stay within a fixed scratch budget, the misfit volumes.  The scratch is allocated per call:
 // nothing of the context changes, so the boxes the confirming-pass shortcut of ttsweep_solve remembers, its pools
@@ -21,7 +21,8 @@ size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
 // (mirrored: tests/test_locate_cpu.py::test_case_constants_mirror_the_sources)
 constexpr long long LOC_PARTIALS = 1LL << 24;
 
-// blocks (group, tile) of one batch of ttsweep_locate_window_device, at most (8 bytes each)
+// blocks (group, tile) of one batch of ttsweep_locate_window_device / ttsweep_locate_subcell_device, at most (8 bytes
+// each) (both mirrored: tests/test_gpu_locate_subcell.py::test_a_batch_edge)
 constexpr long long LOC_WIN_BLOCKS = 1LL << 22;
 
 struct DevScratch {
@@ -31,6 +32,54 @@ struct DevScratch {
         if (p) (void)hipFree(p);
     }
 };
+
+// the windows of the events: lo / hi [nevent][3], or the whole grid of n cells per axis for every event
+struct Windows {
+    const int *lo, *hi;
+    int whole_lo[3], whole_hi[3];
+    Windows(const int *lo, const int *hi, const int *n) : lo(lo), hi(hi), whole_lo{0, 0, 0}, whole_hi{n[0] - 1, n[1] - 1, n[2] - 1} {}
+    const int *lo_of(int e) const { return lo ? lo + 3LL * e : whole_lo; }
+    const int *hi_of(int e) const { return hi ? hi + 3LL * e : whole_hi; }
+    // the events from e on that share its window, at most LOC_WIN_ET: one group
+    int run(int e, int nevent) const
+    {
+        int ne = 1;
+        while (ne < LOC_WIN_ET && e + ne < nevent && !memcmp(lo_of(e + ne), lo_of(e), 3 * sizeof(int)) &&
+               !memcmp(hi_of(e + ne), hi_of(e), 3 * sizeof(int)))
+            ne++;
+        return ne;
+    }
+};
+
+// groups [g0, g1) of one batch, with its partials, blocks and events
+struct Batch {
+    size_t g0, g1;
+    long long parts, blocks;
+    int ne;
+};
+
+// the groups (WinGroup or SubGroup) cut into batches whose partials stay within LOC_PARTIALS and whose block table
+// within LOC_WIN_BLOCKS entries; a group beyond either on its own is a batch
+template <typename Group>
+std::vector<Batch> cut_batches(const std::vector<Group> &groups)
+{
+    std::vector<Batch> batches;
+    for (size_t g = 0; g < groups.size();) {
+        Batch b{g, g, 0, 0, 0};
+        while (b.g1 < groups.size()) {
+            const Group &G = groups[b.g1];
+            if (b.g1 > b.g0 && (b.parts + (long long)G.ne * G.ntiles > LOC_PARTIALS || b.blocks + G.ntiles > LOC_WIN_BLOCKS))
+                break;
+            b.parts += (long long)G.ne * G.ntiles;
+            b.blocks += G.ntiles;
+            b.g1++;
+        }
+        b.ne = groups[b.g1 - 1].e0 + groups[b.g1 - 1].ne - groups[b.g0].e0;
+        batches.push_back(b);
+        g = b.g1;
+    }
+    return batches;
+}
 
 } // namespace
 
@@ -139,24 +188,18 @@ int ttsweep_locate_window_device(ttsweep_ctx *ctx, int nbox, const float *const 
     for (int k = 0; k < nbox; k++)
         if (!tt_dev[k]) return set_error("%s: null box pointer %d", what, k);
 
-    // groups, and batches of groups [first group, end group) with their partials, blocks and events
-    const int whole_lo[3] = {0, 0, 0}, whole_hi[3] = {n[0] - 1, n[1] - 1, n[2] - 1};
-    auto win_lo = [&](int e) { return lo ? lo + 3LL * e : whole_lo; };
-    auto win_hi = [&](int e) { return hi ? hi + 3LL * e : whole_hi; };
+    // groups, and batches of groups
+    const Windows win(lo, hi, n);
     const int tile = locate_window_tile_cells();
     // the index steps of the lattice; a stride beyond the grid is never stepped (one node along that axis)
     const int mx = (int)std::min<long long>(st[0], n[0]) * n[1] * n[2], my = (int)std::min<long long>(st[1], n[1]) * n[2];
     const int mz = std::min(st[2], n[2]);
     std::vector<WinGroup> groups;
     for (int e = 0; e < nevent;) {
-        const int *l = win_lo(e), *h = win_hi(e);
-        int ne = 1;
-        while (ne < LOC_WIN_ET && e + ne < nevent && !memcmp(win_lo(e + ne), l, 3 * sizeof(int)) &&
-               !memcmp(win_hi(e + ne), h, 3 * sizeof(int)))
-            ne++;
+        const int *l = win.lo_of(e), *h = win.hi_of(e);
         WinGroup g;
         g.e0 = e;
-        g.ne = ne;
+        g.ne = win.run(e, nevent);
         long long c[3];
         for (int a = 0; a < 3; a++) c[a] = (h[a] - l[a]) / st[a] + 1;
         g.x0 = (l[0] * n[1] + l[1]) * n[2] + l[2];
@@ -166,32 +209,17 @@ int ttsweep_locate_window_device(ttsweep_ctx *ctx, int nbox, const float *const 
         g.ntiles = (g.ncand + tile - 1) / tile;
         g.part = 0;
         groups.push_back(g);
-        e += ne;
+        e += g.ne;
     }
-    struct Batch {
-        size_t g0, g1;
-        long long parts, blocks;
-    };
-    std::vector<Batch> batches;
+    const std::vector<Batch> batches = cut_batches(groups);
     long long maxp = 1, maxb = 1;
     size_t maxg = 1;
     int maxe = 1;
-    for (size_t g = 0; g < groups.size();) {
-        Batch b{g, g, 0, 0};
-        while (b.g1 < groups.size()) {
-            const WinGroup &G = groups[b.g1];
-            if (b.g1 > b.g0 && (b.parts + (long long)G.ne * G.ntiles > LOC_PARTIALS || b.blocks + G.ntiles > LOC_WIN_BLOCKS))
-                break;
-            b.parts += (long long)G.ne * G.ntiles;
-            b.blocks += G.ntiles;
-            b.g1++;
-        }
-        batches.push_back(b);
+    for (const Batch &b : batches) {
         maxp = std::max(maxp, b.parts);
         maxb = std::max(maxb, b.blocks);
         maxg = std::max(maxg, b.g1 - b.g0);
-        maxe = std::max(maxe, groups[b.g1 - 1].e0 + groups[b.g1 - 1].ne - groups[b.g0].e0);
-        g = b.g1;
+        maxe = std::max(maxe, b.ne);
     }
     if (ctx_bind(ctx)) return -1;
 
@@ -260,6 +288,151 @@ int ttsweep_locate_window_device(ttsweep_ctx *ctx, int nbox, const float *const 
                                            d_invw, d_groups, d_blocks, (int)blocks.size(), d_key, d_x, ctx->stream));
         HIPCHK(launch_locate_window_final(d_boxes, nbox, picks_dev, weights_dev, d_invw, e0, ne, d_evpart, d_evnt,
                                           d_key, d_x, cell_dev, misfit_dev, t0_dev, nan_bits, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));      // the host tables are rebuilt for the next batch
+    }
+    return 0;
+}
+
+// Windows and sub are host values, so every refusal that concerns them comes before the device is touched.  Groups
+// and batches as in ttsweep_locate_window_device, over nodes instead of cells.  A group whose window holds at most
+// locate_subcell_stage_floats() floats over all stations is searched by the blocks that stage it in LDS; the two kinds
+// of blocks are listed apart and launched one after the other.  The scratch is 16 bytes per event, 64 per group, 8
+// per block and 12 per partial of the largest batch: nothing grows with the grid.
+int ttsweep_locate_subcell_device(ttsweep_ctx *ctx, int nbox, const float *const *tt_dev, int nevent,
+                                  const double *picks_dev, const double *weights_dev, const int *lo, const int *hi,
+                                  int sub, int *node_dev, double *misfit_dev, double *t0_dev)
+{
+    const char *what = "ttsweep_locate_subcell_device";
+    if (nbox < 1 || nevent < 1 || !tt_dev || !picks_dev) return set_error("%s: null or bad argument", what);
+    if ((long long)nbox * nevent > INT_MAX)
+        return set_error("%s: %d boxes x %d events do not fit int32 pick indices", what, nbox, nevent);
+    if (!lo != !hi) return set_error("%s: lo and hi must both be given or both be NULL", what);
+    if (sub < 1 || sub > 64) return set_error("%s: sub %d is outside 1..64", what, sub);
+    for (long long i = 0; lo && i < 3LL * nevent; i++)
+        if (lo[i] < 0 || lo[i] > hi[i])
+            return set_error("%s: event %d has a bad window [%d, %d] along axis %d", what, (int)(i / 3), lo[i], hi[i],
+                             (int)(i % 3));
+    if (!ctx) return set_error("%s: null or bad argument", what);
+    const long long ncells = (long long)ctx->nx * ctx->ny * ctx->nz;
+    if (ncells > INT_MAX)
+        return set_error("%s: %d x %d x %d cells do not fit int32 indices", what, ctx->nx, ctx->ny, ctx->nz);
+    const int n[3] = {ctx->nx, ctx->ny, ctx->nz};
+    for (long long i = 0; hi && i < 3LL * nevent; i++)
+        if (hi[i] >= n[i % 3])
+            return set_error("%s: event %d has a window [%d, %d] along axis %d that leaves the grid (%d cells)", what,
+                             (int)(i / 3), lo[i], hi[i], (int)(i % 3), n[i % 3]);
+    for (int a = 0; a < 3; a++)
+        if ((long long)(n[a] - 1) * sub > INT_MAX)
+            return set_error("%s: the nodes of %d cells at sub %d along axis %d do not fit int32", what, n[a], sub, a);
+    for (int k = 0; k < nbox; k++)
+        if (!tt_dev[k]) return set_error("%s: null box pointer %d", what, k);
+
+    const Windows win(lo, hi, n);
+    const int tile = locate_subcell_tile_nodes();
+    std::vector<SubGroup> groups;
+    for (int e = 0; e < nevent;) {
+        const int *l = win.lo_of(e), *h = win.hi_of(e);
+        SubGroup g;
+        g.e0 = e;
+        g.ne = win.run(e, nevent);
+        long long c[3], w[3];
+        for (int a = 0; a < 3; a++) {
+            w[a] = h[a] - l[a] + 1;
+            c[a] = (w[a] - 1) * sub + 1;                // at most INT_MAX each
+            g.lo[a] = l[a];
+        }
+        if (c[0] * c[1] > INT_MAX || c[0] * c[1] * c[2] > INT_MAX)
+            return set_error("%s: event %d has %lld x %lld x %lld nodes, more than fit int32 indices", what, e, c[0],
+                             c[1], c[2]);
+        g.x0 = (l[0] * n[1] + l[1]) * n[2] + l[2];
+        g.wy = (int)w[1];
+        g.wz = (int)w[2];
+        g.wn = (int)(w[0] * w[1] * w[2]);               // at most ncells
+        g.ny = (int)c[1];
+        g.nz = (int)c[2];
+        g.nnode = (int)(c[0] * c[1] * c[2]);
+        g.ntiles = (g.nnode + tile - 1) / tile;
+        g.staged = (long long)nbox * g.wn <= locate_subcell_stage_floats();
+        g.part = 0;
+        groups.push_back(g);
+        e += g.ne;
+    }
+    const std::vector<Batch> batches = cut_batches(groups);
+    long long maxp = 1, maxb = 1;
+    size_t maxg = 1;
+    int maxe = 1;
+    for (const Batch &b : batches) {
+        maxp = std::max(maxp, b.parts);
+        maxb = std::max(maxb, b.blocks);
+        maxg = std::max(maxg, b.g1 - b.g0);
+        maxe = std::max(maxe, b.ne);
+    }
+    if (ctx_bind(ctx)) return -1;
+
+    const size_t bb = align_up(nbox * sizeof(float *)), bi = align_up(nevent * sizeof(double));
+    const size_t bf = align_up(nevent * sizeof(int)), bg = align_up(maxg * sizeof(SubGroup));
+    const size_t bl = align_up((size_t)maxb * sizeof(WinBlock)), bn = align_up((size_t)maxe * sizeof(int));
+    const size_t bk = align_up((size_t)maxp * sizeof(unsigned long long)), bx = align_up((size_t)maxp * sizeof(int));
+    DevScratch S;
+    HIPCHK(hipMalloc((void **)&S.p, bb + bi + bf + bg + bl + bn + bk + bx));
+    char *p = S.p;
+    auto take = [&p](size_t bytes) {
+        char *q = p;
+        p += bytes;
+        return q;
+    };
+    const float **d_boxes = (const float **)take(bb);
+    double *d_invw = (double *)take(bi);
+    int *d_flag = (int *)take(bf);
+    SubGroup *d_groups = (SubGroup *)take(bg);
+    WinBlock *d_blocks = (WinBlock *)take(bl);
+    int *d_evgroup = (int *)take(bn);
+    unsigned long long *d_key = (unsigned long long *)take(bk);
+    int *d_x = (int *)take(bx);
+
+    HIPCHK(hipMemcpyAsync(d_boxes, tt_dev, nbox * sizeof(float *), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(launch_locate_check(nbox, nevent, picks_dev, weights_dev, d_invw, d_flag, ctx->stream));
+    std::vector<int> flag(nevent);
+    HIPCHK(hipMemcpyAsync(flag.data(), d_flag, nevent * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int e = 0; e < nevent; e++) {
+        if (flag[e] & 1) return set_error("%s: event %d has a NaN or infinite pick", what, e);
+        if (flag[e] & 2) return set_error("%s: event %d has a negative, NaN or infinite weight", what, e);
+        if (flag[e] & 4) return set_error("%s: event %d has no weight above zero", what, e);
+    }
+    if (!node_dev && !misfit_dev && !t0_dev) return 0;
+
+    const unsigned long long nan_bits = 0x7ff8000000000000ULL;     // as ttsweep_locate_device
+    const int gnyz = n[1] * n[2], gnz = n[2];
+    std::vector<WinBlock> blocks, unstaged;
+    std::vector<int> evgroup;
+    for (const Batch &b : batches) {
+        blocks.clear();
+        unstaged.clear();
+        evgroup.clear();
+        long long part = 0;
+        for (size_t g = b.g0; g < b.g1; g++) {
+            SubGroup &G = groups[g];
+            G.part = part;
+            part += (long long)G.ne * G.ntiles;
+            evgroup.insert(evgroup.end(), G.ne, (int)(g - b.g0));
+            for (int t = 0; t < G.ntiles; t++) (G.staged ? blocks : unstaged).push_back(WinBlock{(int)(g - b.g0), t});
+        }
+        const int nstaged = (int)blocks.size(), nunstaged = (int)unstaged.size();
+        blocks.insert(blocks.end(), unstaged.begin(), unstaged.end());
+        const int e0 = groups[b.g0].e0;
+        HIPCHK(hipMemcpyAsync(d_groups, groups.data() + b.g0, (b.g1 - b.g0) * sizeof(SubGroup), hipMemcpyHostToDevice,
+                              ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_blocks, blocks.data(), blocks.size() * sizeof(WinBlock), hipMemcpyHostToDevice,
+                              ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_evgroup, evgroup.data(), b.ne * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(launch_locate_subcell_search(d_boxes, nbox, gnyz, gnz, sub, picks_dev, weights_dev, d_invw, d_groups,
+                                            d_blocks, nstaged, true, d_key, d_x, ctx->stream));
+        HIPCHK(launch_locate_subcell_search(d_boxes, nbox, gnyz, gnz, sub, picks_dev, weights_dev, d_invw, d_groups,
+                                            d_blocks + nstaged, nunstaged, false, d_key, d_x, ctx->stream));
+        HIPCHK(launch_locate_subcell_final(d_boxes, nbox, gnyz, gnz, sub, picks_dev, weights_dev, d_invw, e0, b.ne,
+                                           d_evgroup, d_groups, d_key, d_x, node_dev, misfit_dev, t0_dev, nan_bits,
+                                           ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));      // the host tables are rebuilt for the next batch
     }
     return 0;

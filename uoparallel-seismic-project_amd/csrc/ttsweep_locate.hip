@@ -14,6 +14,8 @@
 //   locate_final_kernel     one block per event: the smallest (J bits, x) over the tiles, then t0 at that cell
 //   locate_volume_kernel    J (+INF where inadmissible) of every cell for a list of events
 //   locate_window_*_kernel  the same search over a window and lattice per event ("locate window", further down)
+//   locate_subcell_*_kernel the search over the nodes of a finer lattice inside a window of cells, the station times
+//                           interpolated trilinearly ("locate subcell", further down)
 // A cell is inadmissible when a picked station has T >= +INFINITY or J is not below +INFINITY.  The first implies
 // the second in IEEE arithmetic (o - INF = -INF enters S1, so t0 is -INF or NaN and r of that station is NaN), so
 // one test on the bits of J covers both: J >= 0 always, and +INF and every NaN compare above it as unsigned
@@ -407,6 +409,219 @@ locate_window_final_kernel(const float *const *__restrict__ boxes, int K, const 
     if (t0out) t0out[e] = tb;
 }
 
+// ---- sub-cell search (include/ttsweep.h, "locate subcell") ----
+// The candidates of an event are the nodes of a lattice of `sub` steps per cell edge inside its window of cells; the
+// travel time of a station at a node is the trilinear interpolation of the eight cells around it, in double, seven
+// lerps a + u * (b - a) with every operation rounded on its own.  Groups (SubGroup), the block table and the partials
+// are those of the windowed search.  A lane decodes its node number q (z fastest, relative to the window) once per
+// step, with five divisions: the base cell, which of its three upper neighbours differ from it (f != 0) and ux, uy,
+// uz.  It interpolates the K station times once into the register instance and scores the events of the group on
+// them with loc_misfit.  q ascends with (qx, qy, qz), so the strict compare of a lane and the lexicographic minimum of
+// (bits of J, q) give the smallest node among those of minimal J whatever the grouping.
+//   locate_subcell_search_kernel<KR, STAGED>  one block per WinBlock.  STAGED: the block first copies the window's
+//                                cells of every station to LDS (K * wn <= LOC_SUB_STAGE floats, decided by the host per
+//                                group) and the eight corners are LDS reads; neighbouring nodes share them.  Otherwise
+//                                the corners are read from the boxes.  Both write the partial of event i of the
+//                                group at [group.part + i * group.ntiles + tile]
+//   locate_subcell_final_kernel  one block per event: the smallest of its partials, the node and t0 at it
+// (mirrored: tests/test_gpu_locate_subcell.py::test_node_counts_around_the_tile and ::test_both_corner_paths)
+constexpr int LOC_SC = 8;               // nodes per lane per sub-cell block: a tile is LOC_SC * LOC_BLOCK nodes
+constexpr int LOC_SUB_STAGE = 4096;     // floats of a window (stations x cells) a block stages in LDS, at most
+
+__device__ __forceinline__ double loc_lerp(double a, double b, double u) { return a + u * (b - a); }
+
+// a node as its base cell b (an offset from the window's lo corner in the layout the corners are read from), the
+// offsets dx, dy, dz to the upper neighbour along each axis (0 where f == 0: the upper corner is the base cell and
+// nothing past the window is read) and the three weights
+struct SubNode {
+    int b, dx, dy, dz;
+    double ux, uy, uz;
+};
+
+// node q of a window of ny x nz nodes along y and z; sx, sy: the offset steps of a cell along x and y
+__device__ __forceinline__ SubNode sub_decode(unsigned q, unsigned ny, unsigned nz, unsigned sub, int sx, int sy,
+                                              unsigned &qx, unsigned &qy, unsigned &qz)
+{
+    const unsigned qxy = q / nz;
+    qz = q - qxy * nz;
+    qx = qxy / ny;
+    qy = qxy - qx * ny;
+    const unsigned ix = qx / sub, iy = qy / sub, iz = qz / sub;
+    const unsigned fx = qx - ix * sub, fy = qy - iy * sub, fz = qz - iz * sub;
+    SubNode n;
+    n.b = (int)ix * sx + (int)iy * sy + (int)iz;
+    n.dx = fx ? sx : 0;
+    n.dy = fy ? sy : 0;
+    n.dz = fz ? 1 : 0;
+    n.ux = (double)fx / (double)sub;
+    n.uy = (double)fy / (double)sub;
+    n.uz = (double)fz / (double)sub;
+    return n;
+}
+
+// That of the contract: rd(off) is the station's float at offset off
+template <typename RD>
+__device__ __forceinline__ double sub_time(RD rd, const SubNode &n)
+{
+    const double c00 = loc_lerp((double)rd(n.b), (double)rd(n.b + n.dz), n.uz);
+    const double c01 = loc_lerp((double)rd(n.b + n.dy), (double)rd(n.b + n.dy + n.dz), n.uz);
+    const double c10 = loc_lerp((double)rd(n.b + n.dx), (double)rd(n.b + n.dx + n.dz), n.uz);
+    const double c11 = loc_lerp((double)rd(n.b + n.dx + n.dy), (double)rd(n.b + n.dx + n.dy + n.dz), n.uz);
+    return loc_lerp(loc_lerp(c00, c01, n.uy), loc_lerp(c10, c11, n.uy), n.ux);
+}
+
+template <int KR, bool STAGED>
+__global__ void __launch_bounds__(LOC_BLOCK)
+locate_subcell_search_kernel(const float *const *__restrict__ boxes, int K, int gnyz, int gnz, int sub,
+                             const double *__restrict__ picks, const double *__restrict__ weights,
+                             const double *__restrict__ invw, const SubGroup *__restrict__ groups,
+                             const WinBlock *__restrict__ blocks, unsigned long long *__restrict__ part_key,
+                             int *__restrict__ part_x)
+{
+    __shared__ unsigned long long s_key[LOC_ET][LOC_BLOCK];
+    __shared__ int s_x[LOC_ET][LOC_BLOCK];
+    __shared__ float s_t[STAGED ? LOC_SUB_STAGE : 1];
+    const int tid = threadIdx.x;
+    const WinBlock B = blocks[blockIdx.x];              // uniform: scalar loads
+    const SubGroup G = groups[B.group];
+    const int net = G.ne;
+#pragma unroll
+    for (int i = 0; i < LOC_ET; i++) {
+        s_key[i][tid] = LOC_INF;
+        s_x[i][tid] = 0x7fffffff;
+    }
+    if constexpr (STAGED) {                             // s_t[k * wn + c]: cell c of the window (z fastest), station k
+        for (int p = tid; p < K * G.wn; p += LOC_BLOCK) {
+            const int k = p / G.wn, c = p - k * G.wn;
+            const int cxy = c / G.wz, cz = c - cxy * G.wz;
+            const int cx = cxy / G.wy, cy = cxy - cx * G.wy;
+            s_t[p] = boxes[k][G.x0 + cx * gnyz + cy * gnz + cz];
+        }
+        __syncthreads();
+    }
+    const int sx = STAGED ? G.wy * G.wz : gnyz, sy = STAGED ? G.wz : gnz;
+    auto that = [&](int k, const SubNode &n) {
+        if constexpr (STAGED) {
+            const float *t = s_t + k * G.wn;
+            return sub_time([&](int off) { return t[off]; }, n);
+        } else {
+            const float *t = boxes[k] + G.x0;
+            return sub_time([&](int off) { return t[off]; }, n);
+        }
+    };
+    // uniform loops as in locate_search_kernel: lanes past the last node compute it again and keep nothing
+    const long long base = (long long)B.tile * (LOC_SC * LOC_BLOCK);
+    const int nj = (int)min((long long)LOC_SC, (G.nnode - base + LOC_BLOCK - 1) / LOC_BLOCK);
+    for (int j = 0; j < nj; j++) {
+        const long long ql = base + (long long)j * LOC_BLOCK + tid;
+        const bool in = ql < G.nnode;
+        const int q = in ? (int)ql : G.nnode - 1;
+        unsigned qx, qy, qz;
+        const SubNode n = sub_decode((unsigned)q, (unsigned)G.ny, (unsigned)G.nz, (unsigned)sub, sx, sy, qx, qy, qz);
+        double tr[KR > 0 ? KR : 1];
+        if constexpr (KR > 0) {
+#pragma unroll
+            for (int k = 0; k < KR; k++) tr[k] = k < K ? that(k, n) : 0.0;
+        }
+        for (int i = 0; i < net; i++) {
+            const int e = __builtin_amdgcn_readfirstlane(G.e0 + i);
+            const double *o = picks + (long long)e * K;
+            const double *w = weights ? weights + (long long)e * K : nullptr;
+            double t0;
+            const double J = KR > 0 ? loc_misfit<KR>([&](int k) { return tr[k]; }, K, o, w, invw[e], t0)
+                                    : loc_misfit<0>([&](int k) { return that(k, n); }, K, o, w, invw[e], t0);
+            const unsigned long long key = dbits(J);
+            if (in && key < s_key[i][tid]) {     // nodes of a lane ascend: strict keeps the smallest q
+                s_key[i][tid] = key;
+                s_x[i][tid] = q;
+            }
+        }
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int i = wave; i < net; i += LOC_BLOCK / 64) {
+        unsigned long long key = s_key[i][lane];
+        int x = s_x[i][lane];
+#pragma unroll
+        for (int q = 1; q < LOC_BLOCK / 64; q++) {
+            const unsigned long long k2 = s_key[i][lane + 64 * q];
+            const int x2 = s_x[i][lane + 64 * q];
+            if (loc_less(k2, x2, key, x)) {
+                key = k2;
+                x = x2;
+            }
+        }
+        loc_wave_min(key, x);
+        if (lane == 0) {
+            const long long p = G.part + (long long)i * G.ntiles + B.tile;
+            part_key[p] = key;
+            part_x[p] = x;
+        }
+    }
+}
+
+// one block per event e0 + blockIdx.x, of group ev_group[blockIdx.x]: the smallest (J bits, q) of its partials;
+// node, misfit and t0 (bits) of it, or ((-1, -1, -1), +INF, nan_bits) when no node is admissible
+__global__ void __launch_bounds__(LOC_BLOCK)
+locate_subcell_final_kernel(const float *const *__restrict__ boxes, int K, int gnyz, int gnz, int sub,
+                            const double *__restrict__ picks, const double *__restrict__ weights,
+                            const double *__restrict__ invw, int e0, const int *__restrict__ ev_group,
+                            const SubGroup *__restrict__ groups, const unsigned long long *__restrict__ part_key,
+                            const int *__restrict__ part_x, int *__restrict__ node,
+                            unsigned long long *__restrict__ misfit, unsigned long long *__restrict__ t0out,
+                            unsigned long long nan_bits)
+{
+    __shared__ unsigned long long s_key[LOC_BLOCK / 64];
+    __shared__ int s_x[LOC_BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int e = e0 + blockIdx.x;
+    const SubGroup G = groups[ev_group[blockIdx.x]];
+    const long long p0 = G.part + (long long)(e - G.e0) * G.ntiles;
+    unsigned long long key = LOC_INF;
+    int x = 0x7fffffff;
+    for (int t = tid; t < G.ntiles; t += LOC_BLOCK)
+        if (loc_less(part_key[p0 + t], part_x[p0 + t], key, x)) {
+            key = part_key[p0 + t];
+            x = part_x[p0 + t];
+        }
+    loc_wave_min(key, x);
+    if (lane == 0) {
+        s_key[wave] = key;
+        s_x[wave] = x;
+    }
+    __syncthreads();
+    if (tid) return;
+    key = s_key[0];
+    x = s_x[0];
+    for (int q = 1; q < LOC_BLOCK / 64; q++)
+        if (loc_less(s_key[q], s_x[q], key, x)) {
+            key = s_key[q];
+            x = s_x[q];
+        }
+    const bool found = key < LOC_INF;
+    unsigned long long tb = nan_bits;
+    int qn[3] = {-1, -1, -1};
+    if (found) {
+        unsigned qx, qy, qz;
+        const SubNode n = sub_decode((unsigned)x, (unsigned)G.ny, (unsigned)G.nz, (unsigned)sub, gnyz, gnz, qx, qy, qz);
+        qn[0] = G.lo[0] * sub + (int)qx;
+        qn[1] = G.lo[1] * sub + (int)qy;
+        qn[2] = G.lo[2] * sub + (int)qz;
+        const double *o = picks + (long long)e * K;
+        const double *w = weights ? weights + (long long)e * K : nullptr;
+        double t0;
+        loc_misfit<0>([&](int k) {
+            const float *t = boxes[k] + G.x0;
+            return sub_time([&](int off) { return t[off]; }, n);
+        }, K, o, w, invw[e], t0);
+        tb = dbits(t0);
+    }
+    if (node)
+        for (int a = 0; a < 3; a++) node[3LL * e + a] = qn[a];
+    if (misfit) misfit[e] = found ? key : LOC_INF;
+    if (t0out) t0out[e] = tb;
+}
+
 // ---- confidence regions (include/ttsweep.h, "locate confidence") ----
 // R(e, l) = { x admissible and J(x) <= m[e] + delta[e][l] }, summarised without a volume.  J >= +0 on every cell, so
 // "admissible and J <= thr" is one unsigned compare of the bits of J with an exclusive limit:
@@ -721,6 +936,57 @@ hipError_t launch_locate_window_final(const float *const *boxes, int K, const do
     if (ne <= 0) return hipSuccess;
     hipLaunchKernelGGL(locate_window_final_kernel, dim3(ne), dim3(LOC_BLOCK), 0, st, boxes, K, picks, weights, invw, e0,
                        ev_part, ev_ntiles, part_key, part_x, cell, (unsigned long long *)misfit,
+                       (unsigned long long *)t0, nan_bits);
+    return hipGetLastError();
+}
+
+int locate_subcell_tile_nodes() { return LOC_SC * LOC_BLOCK; }
+int locate_subcell_stage_floats() { return LOC_SUB_STAGE; }
+
+template <bool STAGED>
+static void launch_subcell_search_kr(dim3 grid, hipStream_t st, const float *const *boxes, int K, int gnyz, int gnz,
+                                     int sub, const double *picks, const double *weights, const double *invw,
+                                     const SubGroup *groups, const WinBlock *blocks, unsigned long long *part_key,
+                                     int *part_x)
+{
+    switch (loc_kr(K)) {
+    case 8: hipLaunchKernelGGL((locate_subcell_search_kernel<8, STAGED>), grid, dim3(LOC_BLOCK), 0, st, boxes, K, gnyz,
+                               gnz, sub, picks, weights, invw, groups, blocks, part_key, part_x); break;
+    case 16: hipLaunchKernelGGL((locate_subcell_search_kernel<16, STAGED>), grid, dim3(LOC_BLOCK), 0, st, boxes, K, gnyz,
+                                gnz, sub, picks, weights, invw, groups, blocks, part_key, part_x); break;
+    case 24: hipLaunchKernelGGL((locate_subcell_search_kernel<24, STAGED>), grid, dim3(LOC_BLOCK), 0, st, boxes, K, gnyz,
+                                gnz, sub, picks, weights, invw, groups, blocks, part_key, part_x); break;
+    case 32: hipLaunchKernelGGL((locate_subcell_search_kernel<32, STAGED>), grid, dim3(LOC_BLOCK), 0, st, boxes, K, gnyz,
+                                gnz, sub, picks, weights, invw, groups, blocks, part_key, part_x); break;
+    default: hipLaunchKernelGGL((locate_subcell_search_kernel<0, STAGED>), grid, dim3(LOC_BLOCK), 0, st, boxes, K, gnyz,
+                                gnz, sub, picks, weights, invw, groups, blocks, part_key, part_x); break;
+    }
+}
+
+hipError_t launch_locate_subcell_search(const float *const *boxes, int K, int gnyz, int gnz, int sub,
+                                        const double *picks, const double *weights, const double *invw,
+                                        const SubGroup *groups, const WinBlock *blocks, int nblocks, bool staged,
+                                        unsigned long long *part_key, int *part_x, hipStream_t st)
+{
+    if (nblocks <= 0) return hipSuccess;
+    if (staged)
+        launch_subcell_search_kr<true>(dim3(nblocks), st, boxes, K, gnyz, gnz, sub, picks, weights, invw, groups,
+                                       blocks, part_key, part_x);
+    else
+        launch_subcell_search_kr<false>(dim3(nblocks), st, boxes, K, gnyz, gnz, sub, picks, weights, invw, groups,
+                                        blocks, part_key, part_x);
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_subcell_final(const float *const *boxes, int K, int gnyz, int gnz, int sub,
+                                       const double *picks, const double *weights, const double *invw, int e0, int ne,
+                                       const int *ev_group, const SubGroup *groups,
+                                       const unsigned long long *part_key, const int *part_x, int *node,
+                                       double *misfit, double *t0, unsigned long long nan_bits, hipStream_t st)
+{
+    if (ne <= 0) return hipSuccess;
+    hipLaunchKernelGGL(locate_subcell_final_kernel, dim3(ne), dim3(LOC_BLOCK), 0, st, boxes, K, gnyz, gnz, sub, picks,
+                       weights, invw, e0, ev_group, groups, part_key, part_x, node, (unsigned long long *)misfit,
                        (unsigned long long *)t0, nan_bits);
     return hipGetLastError();
 }

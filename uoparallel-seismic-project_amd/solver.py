@@ -282,6 +282,22 @@ class TravelTimeSolver:
             _require(tuple(weights.shape) == (E, K), f"weights: shape {tuple(weights.shape)}, want {(E, K)}")
         return K, E, dev, picks, weights
 
+    @staticmethod
+    def _windows(E, lo, hi):
+        """(lo, hi) of a windowed call as contiguous int32 [E,3], or (None, None): each given as [3] (every event) or
+        [E,3] integers, numpy or lists."""
+        _require((lo is None) == (hi is None), "lo and hi: both or neither")
+
+        def window(a, what):
+            if a is None:
+                return None
+            a = np.asarray(a)
+            _require(a.dtype.kind in "iu" and a.shape in ((3,), (E, 3)), f"{what}: integers, [3] or [{E}, 3]")
+            _require(a.size == 0 or (a.min() >= -2**31 and a.max() < 2**31), f"{what}: int32 values")
+            return np.ascontiguousarray(np.broadcast_to(a, (E, 3)), dtype=np.int32)
+
+        return window(lo, "lo"), window(hi, "hi")
+
     def _cell_xyz(self, cell):
         """[E,3] int32 on the host: the FLOATBOX indices as (x, y, z), (-1, -1, -1) for -1."""
         import torch
@@ -299,17 +315,7 @@ class TravelTimeSolver:
         the smallest index among those of minimal J.  volumes is None in the result."""
         import torch
         K, E, dev, picks, weights = self._locate_inputs(tt, picks, weights)
-        _require((lo is None) == (hi is None), "lo and hi: both or neither")
-
-        def window(a, what):
-            if a is None:
-                return None
-            a = np.asarray(a)
-            _require(a.dtype.kind in "iu" and a.shape in ((3,), (E, 3)), f"{what}: integers, [3] or [{E}, 3]")
-            _require(a.size == 0 or (a.min() >= -2**31 and a.max() < 2**31), f"{what}: int32 values")
-            return np.ascontiguousarray(np.broadcast_to(a, (E, 3)), dtype=np.int32)
-
-        lo, hi = window(lo, "lo"), window(hi, "hi")
+        lo, hi = self._windows(E, lo, hi)
         stride = np.asarray(stride)
         _require(stride.dtype.kind in "iu" and stride.shape in ((), (3,)), "stride: an int or [3] integers")
         _require(stride.min() >= -2**31 and stride.max() < 2**31, "stride: int32 values")
@@ -348,6 +354,56 @@ class TravelTimeSolver:
         hi = np.where(placed, np.minimum(xyz + radius, n - 1), n - 1)
         fine = self.locate_window(tt, picks, weights, lo=lo, hi=hi, stride=1)
         fine.coarse_cell, fine.coarse_misfit = coarse.cell, coarse.misfit
+        return fine
+
+    def locate_subcell(self, tt, picks, weights=None, lo=None, hi=None, sub=8) -> "SubcellLocations":
+        """ttsweep_locate_subcell_device: the search of locate over the nodes of a lattice of `sub` steps per cell edge
+        inside a window of cells, the station times interpolated trilinearly (include/ttsweep.h, "locate subcell").
+        tt, picks, weights as for locate.  lo, hi: the inclusive window in cells as [3] (every event) or [E,3]
+        integers; both None: the whole grid.  sub: 1..64.  Node q stands for the position q / sub in cells."""
+        import torch
+        K, E, dev, picks, weights = self._locate_inputs(tt, picks, weights)
+        lo, hi = self._windows(E, lo, hi)
+        _require(isinstance(sub, (int, np.integer)) and -2**31 <= sub < 2**31, "sub: an int")
+        node = torch.empty((E, 3), dtype=torch.int32, device=dev)
+        misfit = torch.empty(E, dtype=torch.float64, device=dev)
+        t0 = torch.empty(E, dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.ttsweep_locate_subcell_device(
+            self._ctx, K, self._box_pointers(tt, K), E, picks.data_ptr(),
+            None if weights is None else weights.data_ptr(), None if lo is None else lo.ctypes.data,
+            None if hi is None else hi.ctypes.data, int(sub), node.data_ptr(), misfit.data_ptr(), t0.data_ptr()),
+            "ttsweep_locate_subcell_device")
+        q = node.cpu().numpy()
+        position = np.where(q < 0, np.nan, q.astype(np.float64) / float(sub))
+        return SubcellLocations(node, int(sub), position, misfit, t0)
+
+    def locate_fine(self, tt, picks, weights=None, sub=8, radius=1, cells=None) -> "SubcellLocations":
+        """Sub-cell location around the best cell: locate_subcell on the window cell +- radius (an int or [3]), clipped
+        to the grid.  cells: int32 [E] FLOATBOX indices of an earlier search (locate, locate_window, locate_refine),
+        numpy or on the device, -1 for an event it did not place; None: locate is run here.  An event with cell -1
+        gets the window of cell (0, 0, 0) alone and stays unplaced, which is exact: no cell is admissible for it, every
+        node has its base cell as a corner, so no node is admissible either.  The result carries cell and cell_misfit
+        of the first stage (cell_misfit is None when cells was given); the cell is inside its window, so
+        misfit <= its misfit."""
+        n = np.asarray(self.shape, dtype=np.int64)
+        radius = np.broadcast_to(np.asarray(radius), (3,))
+        _require(radius.dtype.kind in "iu" and radius.min() >= 0, "radius: a non-negative int or [3] integers")
+        _, E, _, picks, weights = self._locate_inputs(tt, picks, weights)       # copied to the device once
+        cell_misfit = None
+        if cells is None:
+            first = self.locate(tt, picks, weights)
+            cells, cell_misfit = first.cell, first.misfit
+        c = _host(cells)
+        _require(c.dtype.kind in "iu" and c.shape == (E,), f"cells: integers [{E}]")
+        c = c.astype(np.int64)
+        _require(c.min() >= -1 and c.max() < int(np.prod(n)), "cells: FLOATBOX indices of this grid, or -1")
+        placed = (c >= 0)[:, None]
+        xyz = np.stack(np.unravel_index(np.maximum(c, 0), self.shape), 1).astype(np.int64)
+        lo = np.where(placed, np.maximum(xyz - radius, 0), 0)
+        hi = np.where(placed, np.minimum(xyz + radius, n - 1), 0)
+        fine = self.locate_subcell(tt, picks, weights, lo=lo, hi=hi, sub=sub)
+        fine.cell, fine.cell_misfit = cells, cell_misfit
         return fine
 
     def locate_confidence(self, tt, picks, weights, misfit, delta) -> "ConfidenceRegions":
@@ -446,6 +502,29 @@ class Locations:
 
     def __len__(self):
         return len(self.cell)
+
+
+@dataclass
+class SubcellLocations:
+    """Events located by TravelTimeSolver.locate_subcell (include/ttsweep.h, "locate subcell"), E events.
+      node     [E,3] int32 (device): the best node (qx, qy, qz), (-1, -1, -1) when no node is admissible
+      sub      lattice steps per cell edge
+      position [E,3] float64 (host): node / sub, the hypocentre in cells; NaN rows where node is -1
+      misfit   [E] float64 (device): J at the node, +inf when there is none
+      t0       [E] float64 (device): the origin time at the node, NaN when there is none
+    locate_fine adds
+      cell, cell_misfit: cell ([E] int32) and misfit ([E] float64, device) of the first stage; cell_misfit is None
+      when the cells were given by the caller"""
+    node: "object"
+    sub: int
+    position: "object"
+    misfit: "object"
+    t0: "object"
+    cell: "object" = None
+    cell_misfit: "object" = None
+
+    def __len__(self):
+        return len(self.node)
 
 
 def _host(a):
