@@ -76,10 +76,13 @@ def main():
     ap.add_argument("--events", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-dense", action="store_true")
+    ap.add_argument("--lib", default=None, help="another build of libttsweep.so (A/B builds)")
     args = ap.parse_args()
     import torch
     import ttsweep_pkg
     P = ttsweep_pkg.load()
+    if args.lib:
+        P._lib.use_library(args.lib)
     nx, ny, nz = (int(x) for x in args.grid.split(","))
     shape = (nx, ny, nz)
     dev = torch.device("cuda:0")
@@ -123,6 +126,7 @@ def main():
             out.update({"confidence_dense_ms": round(ms, 3), "confidence_dense_ms_all": allms,
                         "dense_over_sparse_l1": round(ms / out["confidence_ms_l1"], 3),
                         "dense_inside_share": float(res.count.double().mean() / N)})
+    out["library"] = os.path.relpath(P._lib.LIB_PATH, ROOT)
     print(json.dumps(out))
 
 

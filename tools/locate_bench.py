@@ -73,10 +73,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--chunk", type=int, default=8)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--lib", default=None, help="another build of libttsweep.so (A/B builds)")
     args = ap.parse_args()
     import torch
     import ttsweep_pkg
     P = ttsweep_pkg.load()
+    if args.lib:
+        P._lib.use_library(args.lib)
     nx, ny, nz = (int(x) for x in args.grid.split(","))
     shape = (nx, ny, nz)
     dev = torch.device("cuda:0")
@@ -127,6 +130,7 @@ def main():
             out.update({"torch_ms": round(torch_ms, 1), "torch_chunk_events": args.chunk,
                         "speedup_over_torch": round(torch_ms / loc_ms, 2),
                         "torch_cells_agree": round(float((tc.to(torch.int32) == res.cell).double().mean()), 4)})
+    out["library"] = os.path.relpath(P._lib.LIB_PATH, ROOT)
     print(json.dumps(out))
 
 

@@ -80,10 +80,13 @@ def main():
     ap.add_argument("--events", type=int, default=4096)
     ap.add_argument("--sub", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--lib", default=None, help="another build of libttsweep.so (A/B builds)")
     args = ap.parse_args()
     import torch
     import ttsweep_pkg
     P = ttsweep_pkg.load()
+    if args.lib:
+        P._lib.use_library(args.lib)
     nx, ny, nz = (int(x) for x in args.grid.split(","))
     shape = (nx, ny, nz)
     n = np.array(shape, np.int64)
@@ -153,6 +156,7 @@ def main():
                "triple_ratio": round(ratio, 3), "count_ratio": round((21 * K + 8 * kp) / (8 * kp), 3),
                "accuracy_events": int(len(pos)), "median_distance_cell": d_cell,
                "median_distance_centroid": d_centroid, "median_distance_fine": d_fine}
+    out["library"] = os.path.relpath(P._lib.LIB_PATH, ROOT)
     print(json.dumps(out))
     if not d_fine < d_cell:
         sys.exit(f"locate_fine's median distance ({d_fine}) is not below locate's ({d_cell})")

@@ -54,10 +54,13 @@ def main():
     ap.add_argument("--events", type=int, default=4096)
     ap.add_argument("--stride", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--lib", default=None, help="another build of libttsweep.so (A/B builds)")
     args = ap.parse_args()
     import torch
     import ttsweep_pkg
     P = ttsweep_pkg.load()
+    if args.lib:
+        P._lib.use_library(args.lib)
     nx, ny, nz = (int(x) for x in args.grid.split(","))
     shape = (nx, ny, nz)
     n = np.array(shape, np.int64)
@@ -113,6 +116,7 @@ def main():
                "refined_equal": round(float((fine.cell == full.cell).double().mean()), 4),
                "max_misfit_excess": float(excess.max()) if len(excess) else 0.0,
                "coarse_without_cell": int((coarse.cell < 0).sum())}
+    out["library"] = os.path.relpath(P._lib.LIB_PATH, ROOT)
     print(json.dumps(out))
     if not ref_ms < loc_ms:
         sys.exit(f"locate_refine ({ref_ms:.3f} ms) is not faster than locate ({loc_ms:.3f} ms)")

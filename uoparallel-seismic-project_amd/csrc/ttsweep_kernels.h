@@ -179,10 +179,11 @@ hipError_t launch_ray_adjoint(const RayGeom &G, const float *v, const RayBox *bo
 // g[x] = ldexp((double)acc[x], -S) in place
 hipError_t launch_ray_fixed_to_double(long long *g, long long n, int S, hipStream_t st);
 
-// event location (ttsweep_locate.hip).  check: invw[e] = 1.0 / W and flag[e] (bit 0 a non-finite pick, bit 1 a
-// negative or non-finite weight, bit 2 no weight above zero) of every event; search: the per-tile partials
-// [(e - e0) * ntiles + tile] of events e0 .. e0 + ne - 1; final: cell / misfit / t0 (each may be nullptr) of those
-// events from the partials; volume: vol[v][x] = J of event vev[v]
+// event location (ttsweep_locate.hip; every search there is one scan, loc_scan, over its own kind of candidate, and
+// the three argmin searches share the per-lane minima and the final).  check: invw[e] = 1.0 / W and flag[e] (bit 0 a
+// non-finite pick, bit 1 a negative or non-finite weight, bit 2 no weight above zero) of every event; search: the
+// per-tile partials [(e - e0) * ntiles + tile] of events e0 .. e0 + ne - 1; final: cell / misfit / t0 (each may be
+// nullptr) of those events from the partials; volume: vol[v][x] = J of event vev[v]
 int locate_tile_cells();
 hipError_t launch_locate_check(int K, int nevent, const double *picks, const double *weights, double *invw, int *flag,
                                hipStream_t st);
@@ -201,8 +202,7 @@ hipError_t launch_locate_volume(const float *const *boxes, int K, int N, const d
 // index x0 + cx * mx + cy * my + cz * mz (x0 the window's lo corner; mx, my, mz = sx * ny * nz, sy * nz, sz the index
 // steps of the lattice), cut into ntiles tiles of locate_window_tile_cells().  The
 // partials of its event i are [part + i * ntiles + tile].  search: one block per entry of the block table; final: cell
-// / misfit / t0 (each may be nullptr) of events e0 .. e0 + ne - 1 from the ev_ntiles[e - e0] partials at
-// ev_part[e - e0]
+// / misfit / t0 (each may be nullptr) of events e0 .. e0 + ne - 1, event e of group ev_group[e - e0]
 constexpr int LOC_WIN_ET = 8;       // events of a group, at most
 struct WinGroup {
     int e0, ne;             // first event and number of events
@@ -220,10 +220,9 @@ hipError_t launch_locate_window_search(const float *const *boxes, int K, int mx,
                                        const WinGroup *groups, const WinBlock *blocks, int nblocks,
                                        unsigned long long *part_key, int *part_x, hipStream_t st);
 hipError_t launch_locate_window_final(const float *const *boxes, int K, const double *picks, const double *weights,
-                                      const double *invw, int e0, int ne, const long long *ev_part,
-                                      const int *ev_ntiles, const unsigned long long *part_key, const int *part_x,
-                                      int *cell, double *misfit, double *t0, unsigned long long nan_bits,
-                                      hipStream_t st);
+                                      const double *invw, int e0, int ne, const int *ev_group, const WinGroup *groups,
+                                      const unsigned long long *part_key, const int *part_x, int *cell, double *misfit,
+                                      double *t0, unsigned long long nan_bits, hipStream_t st);
 
 // sub-cell event location (ttsweep_locate.hip).  A group is up to 8 consecutive events that share one window of
 // wx * wy * wz = wn cells from the FLOATBOX index x0 (cell lo).  Its candidates are the nodes q = (qx * ny + qy) * nz
