@@ -382,6 +382,60 @@ int ttsweep_ray_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start
                                int nrecv, const ttsweep_start *receivers,
                                const double *w_dev, double *g_dev, int *hits_dev, int *scale);
 
+/* ---- rays: pair lists ---------------------------------------------------- */
+/* The data of a tomography are not a cross product: an event is picked at some of the stations, a shot has its own
+ * receiver spread.  These calls take the rays as a list of npair (box, receiver) pairs instead: ray r is the ray of
+ * box pair_box[r] from receiver pair_recv[r], walked exactly as ttsweep_trace_rays_device walks it (the same checks
+ * per hop, the same statuses, the same hop_d choice).  A pair may occur more than once: each occurrence is a ray of
+ * its own.  Arguments ctx, nstart, starts, tt_dev, pred_dev as for ttsweep_ray_forward_device, then
+ *   npair     : the number of pairs
+ *   pair_box  : host, npair entries, each in [0, nstart)
+ *   pair_recv : host, npair receivers (cells inside the grid)
+ * Refused before any device work and before any output is touched: everything ttsweep_ray_forward_device refuses
+ * for the shared arguments, npair < 0, npair > INT32_MAX, a NULL pair_box or pair_recv with npair > 0, a pair_box
+ * outside [0, nstart) and a receiver outside the grid (ttsweep_last_error names the pair); a NaN or infinite weight
+ * is found before g is touched, as in the dense call.  npair == 0 behaves as the dense calls do with nrecv == 0.
+ * The calls change no box and no state of the context.  All return 0, or < 0 with ttsweep_last_error set. */
+#define TTSWEEP_HAS_RAY_PAIRS 1     /* the three calls below exist (TTSWEEP_ABI_VERSION stays 6) */
+
+/* y = G m and g = G^T w with hit counts over the pair list: the semantics of ttsweep_ray_forward_device and
+ * ttsweep_ray_adjoint_device word for word, with nstart*nrecv replaced by npair: y_dev, w_dev and status have npair
+ * entries, K = ceil(log2(npair)) (0 for one ray), S = 61 - E_w - E_d - K.  For the pair list
+ * pair_box[s*nrecv+q] = s, pair_recv[s*nrecv+q] = receivers[q] every output is the dense call's bit for bit.  g, hits
+ * and S do not depend on the order of the pairs (integer sums; S depends on the weights and npair only); y and
+ * status follow it. */
+int ttsweep_ray_pairs_forward_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                     const float *const *tt_dev, const int *const *pred_dev,
+                                     long long npair, const int *pair_box, const ttsweep_start *pair_recv,
+                                     const double *m_dev, double *y_dev, int *status);
+int ttsweep_ray_pairs_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                     const float *const *tt_dev, const int *const *pred_dev,
+                                     long long npair, const int *pair_box, const ttsweep_start *pair_recv,
+                                     const double *w_dev, double *g_dev, int *hits_dev, int *scale);
+
+/* The geometry of every ray of the list, read off the same walk without storing a path.  status: host, npair entries,
+ * may be NULL.  Every *_dev output is on the device, one entry per pair (recv_hop_dev and src_hop_dev: three int32 per
+ * pair, entry 3*r + axis); each may be NULL.  For an OK or SEED ray with hops p -> c in walk order (receiver to
+ * source), q the receiver's FLOATBOX index:
+ *   t_recv   : T[q]; written for every status
+ *   hops     : the number of hops (the path's cells minus 1); 0 for a receiver that is the start or a SEED cell
+ *   length   : from 0.0, length = length + (double)d per hop in walk order, each addition rounded on its own
+ *   recv_hop : the cell offset (p - c) per axis of the first hop, the one out of the receiver: it points from the
+ *              receiver towards the source; recv_d: that hop's d; recv_dt: the one float subtraction T[c] - T[p]
+ *   src_hop  : the offset (c - p) of the last hop, p the cell the walk ends at: it points out of the source;
+ *              src_d: that hop's d; src_dt: T[c] - T[p]
+ *   deep     : the FLOATBOX index of the path cell with the greatest z index, receiver and end cell included; of equal
+ *              ones the first met in walk order
+ * A ray without a hop has zeros in both *_hop, *_d and *_dt, and deep = q.  An UNREACHED or INVALID ray has hops = 0,
+ * length = 0.0, zeros in the hop fields and deep = -1 (t_recv is still T[q]).  Every output is an integer or one
+ * singly rounded float or double operation. */
+int ttsweep_ray_pairs_geometry_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                      const float *const *tt_dev, const int *const *pred_dev,
+                                      long long npair, const int *pair_box, const ttsweep_start *pair_recv,
+                                      int *status, float *t_recv_dev, int *hops_dev, double *length_dev,
+                                      int *recv_hop_dev, float *recv_d_dev, float *recv_dt_dev,
+                                      int *src_hop_dev, float *src_d_dev, float *src_dt_dev, int *deep_dev);
+
 /* ---- locate: grid-search event location over station travel-time boxes ---- */
 /* By reciprocity, box k solved from station k as its start holds T_k[x], the travel time between the station and a
  * candidate hypocentre x.  For each of nevent events with picks o[e][k] and weights w[e][k] (double, [nevent][nbox],

@@ -179,6 +179,32 @@ hipError_t launch_ray_adjoint(const RayGeom &G, const float *v, const RayBox *bo
 // g[x] = ldexp((double)acc[x], -S) in place
 hipError_t launch_ray_fixed_to_double(long long *g, long long n, int S, hipStream_t st);
 
+// pair lists: ray r is the ray of box pairs[r].box from the cell of FLOATBOX index pairs[r].recv
+struct alignas(8) RayPair {
+    int box, recv;
+};
+// the outputs of the geometry kernel, each [npair] (recv_hop, src_hop: [npair][3]) on the device or nullptr
+struct RayGeometryOut {
+    float *t_recv;
+    int *hops;
+    double *length;
+    int *recv_hop;
+    float *recv_d, *recv_dt;
+    int *src_hop;
+    float *src_d, *src_dt;
+    int *deep;
+};
+// the operators and the geometry over a pair list (status[r] of every pair; acc as in launch_ray_adjoint)
+hipError_t launch_ray_pairs_forward(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
+                                    int npair, const RayEntry *entries, int nentries, bool exact, const double *m,
+                                    double *y, int *status, hipStream_t st);
+hipError_t launch_ray_pairs_adjoint(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
+                                    int npair, const RayEntry *entries, int nentries, bool exact, const double *w,
+                                    int S, long long *acc, int *hits, hipStream_t st);
+hipError_t launch_ray_pairs_geometry(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
+                                     int npair, const RayEntry *entries, int nentries, bool exact, int *status,
+                                     const RayGeometryOut &out, hipStream_t st);
+
 // event location (ttsweep_locate.hip; every search there is one scan, loc_scan, over its own kind of candidate, and
 // the three argmin searches share the per-lane minima and the final).  check: invw[e] = 1.0 / W and flag[e] (bit 0 a
 // non-finite pick, bit 1 a negative or non-finite weight, bit 2 no weight above zero) of every event; search: the

@@ -1,7 +1,7 @@
 // ttsweep_rays.cpp - the ray calls of include/ttsweep.h: ttsweep_predecessors_device,
-// ttsweep_trace_rays_device and the Frechet operators ttsweep_ray_forward_device / ttsweep_ray_adjoint_device
-// (kernels: ttsweep_rays.hip).  Argument checks, the star's ray entries, the
-// host-side scan of the per-ray cell counts.  Nothing here touches the solve's state: the boxes the
+// ttsweep_trace_rays_device, the Frechet operators ttsweep_ray_forward_device / ttsweep_ray_adjoint_device and
+// their pair-list forms ttsweep_ray_pairs_{forward,adjoint,geometry}_device (kernels: ttsweep_rays.hip).
+// Argument checks, the star's ray entries, the host-side scan of the per-ray cell counts.  Nothing here touches the solve's state: the boxes the
 // confirming-pass shortcut of ttsweep_solve remembers, its pools and its options stay as they are.
 #include "ttsweep_ctx.h"
 
@@ -151,6 +151,67 @@ int stage(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float
     return 0;
 }
 
+// the checks of the three pair-list calls before any device work: the pair count (one int32 index per ray), the
+// boxes, every pair; the pairs as device records
+int check_pairs(const ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float *const *tt_dev,
+                const int *const *pred_dev, long long npair, const int *pair_box, const ttsweep_start *pair_recv,
+                const char *what, std::vector<RayPair> &pairs)
+{
+    if (nstart < 0 || npair < 0) return set_error("%s: null or bad argument", what);
+    if (npair > INT_MAX) return set_error("%s: %lld pairs do not fit int32 ray indices", what, npair);
+    if (npair > 0 && (!pair_box || !pair_recv)) return set_error("%s: null or bad argument", what);
+    if (check_boxes(ctx, nstart, starts, tt_dev, (const void *const *)pred_dev, what)) return -1;
+    pairs.resize(npair);
+    for (long long r = 0; r < npair; r++) {
+        if (pair_box[r] < 0 || pair_box[r] >= nstart)
+            return set_error("%s: pair %lld names box %d, not in [0, %d)", what, r, pair_box[r], nstart);
+        if (!inside(ctx, pair_recv[r]))
+            return set_error("%s: receiver of pair %lld (%d, %d, %d) outside the grid", what, r, pair_recv[r].i,
+                             pair_recv[r].j, pair_recv[r].k);
+        pairs[r] = RayPair{pair_box[r], flat(ctx, pair_recv[r])};
+    }
+    return 0;
+}
+
+// The adjoint of nrays rays once the boxes and the rays' records are staged: the weights' scan (a NaN or infinite
+// weight is refused before g is touched), S = 61 - E_w - E_d - K, the zeroed accumulators, launch(w, S) and the
+// conversion of g.  d_scan: two ints of the ray buffer.
+template <class Launch>
+int run_adjoint(ttsweep_ctx *ctx, const char *what, const RayStage &S, long long nrays, int *d_scan,
+                const double *w_dev, double *g_dev, int *hits_dev, int *scale, Launch launch)
+{
+    const long long ncells = (long long)ctx->nx * ctx->ny * ctx->nz;
+    // S = 61 - E_w - E_d - K: a visit adds less than 2^(E_w + E_d + S) = 2^(61 - K) in magnitude, a ray visits a
+    // cell at most once (T strictly decreases along it) and there are at most 2^K rays, so |acc[x]| < 2^61
+    int shift = 0;
+    bool weighted = false;
+    if (w_dev && nrays > 0) {
+        int scan[2] = {0, 0};
+        HIPCHK(hipMemsetAsync(d_scan, 0, 2 * sizeof(int), ctx->stream));
+        HIPCHK(launch_ray_weight_scan(w_dev, (int)nrays, d_scan, ctx->stream));
+        HIPCHK(hipMemcpyAsync(scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (scan[1]) return set_error("%s: a weight is NaN or infinite", what);
+        if (scan[0]) {
+            float dmax = 0.0f;
+            for (const RayEntry &e : S.ent) dmax = std::max(dmax, e.d);
+            int e_d = 0;
+            std::frexp((double)dmax, &e_d);
+            int k = 0;
+            while ((1LL << k) < nrays) k++;
+            shift = 61 - (scan[0] - 2048) - e_d - k;
+            weighted = true;
+        }
+    }
+    if (g_dev) HIPCHK(hipMemsetAsync(g_dev, 0, ncells * sizeof(double), ctx->stream));
+    if (hits_dev) HIPCHK(hipMemsetAsync(hits_dev, 0, ncells * sizeof(int), ctx->stream));
+    if (weighted || hits_dev) HIPCHK(launch(weighted ? w_dev : nullptr, shift));
+    if (weighted) HIPCHK(launch_ray_fixed_to_double((long long *)g_dev, ncells, shift, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (scale) *scale = shift;
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -253,7 +314,6 @@ int ttsweep_ray_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start
     if (check_operator(ctx, nstart, starts, tt_dev, pred_dev, nrecv, receivers, what, recv)) return -1;
     if (!w_dev != !g_dev) return set_error("%s: w and g must both be given or both be NULL", what);
     const long long nrays = (long long)nstart * nrecv;
-    const long long ncells = (long long)ctx->nx * ctx->ny * ctx->nz;
     if (!g_dev && !hits_dev) {
         if (scale) *scale = 0;
         return 0;
@@ -266,37 +326,87 @@ int ttsweep_ray_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start
     int *d_scan = (int *)(S.rest + br);
     if (nrecv)
         HIPCHK(hipMemcpyAsync(d_recv, recv.data(), nrecv * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    // S = 61 - E_w - E_d - K: a visit adds less than 2^(E_w + E_d + S) = 2^(61 - K) in magnitude, a ray visits a
-    // cell at most once (T strictly decreases along it) and there are at most 2^K rays, so |acc[x]| < 2^61
-    int shift = 0;
-    bool weighted = false;
-    if (w_dev && nrays > 0) {
-        int scan[2] = {0, 0};
-        HIPCHK(hipMemsetAsync(d_scan, 0, 2 * sizeof(int), ctx->stream));
-        HIPCHK(launch_ray_weight_scan(w_dev, (int)nrays, d_scan, ctx->stream));
-        HIPCHK(hipMemcpyAsync(scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (scan[1]) return set_error("%s: a weight is NaN or infinite", what);
-        if (scan[0]) {
-            float dmax = 0.0f;
-            for (const RayEntry &e : S.ent) dmax = std::max(dmax, e.d);
-            int e_d = 0;
-            std::frexp((double)dmax, &e_d);
-            int k = 0;
-            while ((1LL << k) < nrays) k++;
-            shift = 61 - (scan[0] - 2048) - e_d - k;
-            weighted = true;
-        }
-    }
-    if (g_dev) HIPCHK(hipMemsetAsync(g_dev, 0, ncells * sizeof(double), ctx->stream));
-    if (hits_dev) HIPCHK(hipMemsetAsync(hits_dev, 0, ncells * sizeof(int), ctx->stream));
-    if (weighted || hits_dev)
-        HIPCHK(launch_ray_adjoint(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, (int)S.ent.size(),
-                                  ctx->exact_half, weighted ? w_dev : nullptr, shift, (long long *)g_dev, hits_dev,
-                                  ctx->stream));
-    if (weighted) HIPCHK(launch_ray_fixed_to_double((long long *)g_dev, ncells, shift, ctx->stream));
+    return run_adjoint(ctx, what, S, nrays, d_scan, w_dev, g_dev, hits_dev, scale, [&](const double *w, int shift) {
+        return launch_ray_adjoint(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, (int)S.ent.size(),
+                                  ctx->exact_half, w, shift, (long long *)g_dev, hits_dev, ctx->stream);
+    });
+}
+
+int ttsweep_ray_pairs_forward_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                     const float *const *tt_dev, const int *const *pred_dev,
+                                     long long npair, const int *pair_box, const ttsweep_start *pair_recv,
+                                     const double *m_dev, double *y_dev, int *status)
+{
+    const char *what = "ttsweep_ray_pairs_forward_device";
+    std::vector<RayPair> pairs;
+    if (check_pairs(ctx, nstart, starts, tt_dev, pred_dev, npair, pair_box, pair_recv, what, pairs)) return -1;
+    if (npair == 0) return 0;
+    if (!m_dev || !y_dev) return set_error("%s: null or bad argument", what);
+    if (ctx_bind(ctx)) return -1;
+    const size_t bp = align_up(npair * sizeof(RayPair)), bn = align_up(npair * sizeof(int));
+    RayStage S;
+    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, bp + bn, S)) return -1;
+    RayPair *d_pairs = (RayPair *)S.rest;
+    int *d_status = (int *)(S.rest + bp);
+    HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), npair * sizeof(RayPair), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(launch_ray_pairs_forward(S.G, ctx->d_v, S.d_boxes, d_pairs, (int)npair, S.d_ent, (int)S.ent.size(),
+                                    ctx->exact_half, m_dev, y_dev, d_status, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d_status, npair * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (scale) *scale = shift;
+    return 0;
+}
+
+int ttsweep_ray_pairs_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                     const float *const *tt_dev, const int *const *pred_dev,
+                                     long long npair, const int *pair_box, const ttsweep_start *pair_recv,
+                                     const double *w_dev, double *g_dev, int *hits_dev, int *scale)
+{
+    const char *what = "ttsweep_ray_pairs_adjoint_device";
+    std::vector<RayPair> pairs;
+    if (check_pairs(ctx, nstart, starts, tt_dev, pred_dev, npair, pair_box, pair_recv, what, pairs)) return -1;
+    if (!w_dev != !g_dev) return set_error("%s: w and g must both be given or both be NULL", what);
+    if (!g_dev && !hits_dev) {
+        if (scale) *scale = 0;
+        return 0;
+    }
+    if (ctx_bind(ctx)) return -1;
+    const size_t bp = align_up(std::max<long long>(npair, 1) * sizeof(RayPair));
+    RayStage S;
+    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, bp + 256, S)) return -1;
+    RayPair *d_pairs = (RayPair *)S.rest;
+    int *d_scan = (int *)(S.rest + bp);
+    if (npair)
+        HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), npair * sizeof(RayPair), hipMemcpyHostToDevice, ctx->stream));
+    return run_adjoint(ctx, what, S, npair, d_scan, w_dev, g_dev, hits_dev, scale, [&](const double *w, int shift) {
+        return launch_ray_pairs_adjoint(S.G, ctx->d_v, S.d_boxes, d_pairs, (int)npair, S.d_ent, (int)S.ent.size(),
+                                        ctx->exact_half, w, shift, (long long *)g_dev, hits_dev, ctx->stream);
+    });
+}
+
+int ttsweep_ray_pairs_geometry_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
+                                      const float *const *tt_dev, const int *const *pred_dev,
+                                      long long npair, const int *pair_box, const ttsweep_start *pair_recv,
+                                      int *status, float *t_recv_dev, int *hops_dev, double *length_dev,
+                                      int *recv_hop_dev, float *recv_d_dev, float *recv_dt_dev,
+                                      int *src_hop_dev, float *src_d_dev, float *src_dt_dev, int *deep_dev)
+{
+    const char *what = "ttsweep_ray_pairs_geometry_device";
+    std::vector<RayPair> pairs;
+    if (check_pairs(ctx, nstart, starts, tt_dev, pred_dev, npair, pair_box, pair_recv, what, pairs)) return -1;
+    if (npair == 0) return 0;
+    if (ctx_bind(ctx)) return -1;
+    const size_t bp = align_up(npair * sizeof(RayPair)), bn = align_up(npair * sizeof(int));
+    RayStage S;
+    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, bp + bn, S)) return -1;
+    RayPair *d_pairs = (RayPair *)S.rest;
+    int *d_status = (int *)(S.rest + bp);
+    HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), npair * sizeof(RayPair), hipMemcpyHostToDevice, ctx->stream));
+    const RayGeometryOut out{t_recv_dev, hops_dev, length_dev, recv_hop_dev, recv_d_dev, recv_dt_dev,
+                             src_hop_dev, src_d_dev, src_dt_dev, deep_dev};
+    HIPCHK(launch_ray_pairs_geometry(S.G, ctx->d_v, S.d_boxes, d_pairs, (int)npair, S.d_ent, (int)S.ent.size(),
+                                     ctx->exact_half, d_status, out, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d_status, npair * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 

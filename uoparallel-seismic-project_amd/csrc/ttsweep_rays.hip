@@ -238,6 +238,9 @@ hipError_t launch_trace_rays(const RayGeom &G, const float *v, const RayBox *box
 // (ray, p) and at (ray, c).  Both kernels walk one lane per ray r = s * nrecv + q like trace_rays_kernel (the
 // same checks per hop, the same statuses, the same hop_length<EXACT> choice of d) and read or scatter along
 // the walk instead of storing it.  UNREACHED and INVALID rays contribute nothing.
+// The ray_pairs_* kernels are the same bodies over a list of (box, receiver) records instead of the cross product,
+// and ray_pairs_geometry_kernel reads the geometry of each ray off the same walk (include/ttsweep.h, "rays: pair
+// lists").
 
 // The walk of trace_rays_kernel from receiver q of box B: hop(c, p, d) for every hop p -> c, in walk order
 // (receiver -> source).  Returns the ray's status; *end is the cell the walk ended at.
@@ -268,7 +271,26 @@ __device__ __forceinline__ int ray_walk(const RayGeom &G, const float *__restric
 }
 
 // y[r] = (G m)[r]: y = y + (0.5 * (double)d) * (m[c] + m[p]) per hop p -> c in walk order from y = 0.0;
-// 0 for UNREACHED and INVALID rays.  One store per ray.
+// 0 for UNREACHED and INVALID rays.  One store per ray.  where(r, s, q): box and flat receiver of ray r (the
+// cross product r = s * nrecv + q of the dense call, or the record of a pair list).
+template <bool EXACT, class Where>
+__device__ __forceinline__ void ray_forward_body(const RayGeom &G, const float *__restrict__ v,
+                                                 const RayBox *__restrict__ boxes,
+                                                 const RayEntry *__restrict__ entries, int nentries, int r,
+                                                 Where where, const double *__restrict__ m,
+                                                 double *__restrict__ y, int *__restrict__ status)
+{
+    int s, q;
+    where(r, s, q);
+    const RayBox B = boxes[s];
+    double acc = 0.0;
+    int end;
+    const int st = ray_walk<EXACT>(G, v, B, entries, nentries, q, &end,
+                                   [&](int c, int p, float d) { acc = acc + (0.5 * (double)d) * (m[c] + m[p]); });
+    y[r] = (st == TTSWEEP_RAY_OK || st == TTSWEEP_RAY_SEED) ? acc : 0.0;
+    status[r] = st;
+}
+
 template <bool EXACT>
 __global__ void __launch_bounds__(RAY_BLOCK)
 ray_forward_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes, int nstart,
@@ -277,14 +299,23 @@ ray_forward_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restr
 {
     const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
     if (r >= nstart * nrecv) return;
-    const int s = r / nrecv;
-    const RayBox B = boxes[s];
-    double acc = 0.0;
-    int end;
-    const int st = ray_walk<EXACT>(G, v, B, entries, nentries, recv[r - s * nrecv], &end,
-                                   [&](int c, int p, float d) { acc = acc + (0.5 * (double)d) * (m[c] + m[p]); });
-    y[r] = (st == TTSWEEP_RAY_OK || st == TTSWEEP_RAY_SEED) ? acc : 0.0;
-    status[r] = st;
+    ray_forward_body<EXACT>(G, v, boxes, entries, nentries, r,
+                            [&](int r, int &s, int &q) { s = r / nrecv; q = recv[r - s * nrecv]; }, m, y, status);
+}
+
+// the same for a pair list: one lane per pair, the record in one 8-byte load
+template <bool EXACT>
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_pairs_forward_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes,
+                         const RayPair *__restrict__ pairs, int npair, const RayEntry *__restrict__ entries,
+                         int nentries, const double *__restrict__ m, double *__restrict__ y,
+                         int *__restrict__ status)
+{
+    const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
+    if (r >= npair) return;
+    ray_forward_body<EXACT>(G, v, boxes, entries, nentries, r,
+                            [&](int r, int &s, int &q) { const RayPair pr = pairs[r]; s = pr.box; q = pr.recv; },
+                            m, y, status);
 }
 
 // The fixed-point term of one visit: llrint(ldexp(w * (0.5 * ((double)d_in + (double)d_out)), S))
@@ -298,25 +329,25 @@ __device__ __forceinline__ long long ray_term(double w, float d_in, float d_out,
 // walk order, and at the end of the walk for the last cell.  An INVALID ray's terms are already added when its
 // walk fails: the same walk again takes them back out (integer adds: exact in any order).  Every OK ray of box
 // s ends at its start cell: those terms and hits are summed across the wave first, one atomic per wave and box.
-// Every lane of a wave reaches the wave sum (no early return).
-template <bool EXACT>
-__global__ void __launch_bounds__(RAY_BLOCK)
-ray_adjoint_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes, int nstart,
-                   const int *__restrict__ recv, int nrecv, const RayEntry *__restrict__ entries, int nentries,
-                   const double *__restrict__ w, int S, unsigned long long *__restrict__ acc,
-                   int *__restrict__ hits)
+// Every lane of a wave reaches the wave sum (no early return).  The wave sum is keyed on the end cell, not on the
+// box: the lanes of one wave may belong to any boxes (a pair list), each distinct start cell gets its own round.
+// where(r, s, q): box and flat receiver of ray r, as in ray_forward_body.
+template <bool EXACT, class Where>
+__device__ __forceinline__ void ray_adjoint_body(const RayGeom &G, const float *__restrict__ v,
+                                                 const RayBox *__restrict__ boxes,
+                                                 const RayEntry *__restrict__ entries, int nentries, int r,
+                                                 int nrays, Where where, const double *__restrict__ w, int S,
+                                                 unsigned long long *__restrict__ acc, int *__restrict__ hits)
 {
-    const int nrays = nstart * nrecv;
-    const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
     const bool lane = r < nrays;
     const double wr = (lane && w) ? w[r] : 0.0;
     const bool weighted = wr != 0.0;
     int st = TTSWEEP_RAY_UNREACHED, end = -1;
     float dlast = 0.0f;
     if (lane && (weighted || hits)) {
-        const int s = r / nrecv;
+        int s, q;
+        where(r, s, q);
         const RayBox B = boxes[s];
-        const int q = recv[r - s * nrecv];
         auto visit = [&](long long sign) {
             float dout = 0.0f;      // the hop out of the cell in the path's direction: none at the receiver
             return [&, sign, dout](int c, int, float d) mutable {
@@ -342,8 +373,8 @@ ray_adjoint_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restr
             if (hits) atomicAdd(hits + end, 1);
         }
     }
-    // the start cells of the OK rays: one wave sum per distinct cell (a wave spans one box unless nrecv < 64
-    // or it straddles a box boundary)
+    // the start cells of the OK rays: one wave sum per distinct cell (in the dense call a wave spans one box
+    // unless nrecv < 64 or it straddles a box boundary; in a pair list it spans whatever boxes its pairs name)
     bool pend = st == TTSWEEP_RAY_OK;
     const long long mine = (pend && weighted) ? ray_term(wr, 0.0f, dlast, S) : 0;
     unsigned long long live = __ballot(pend);
@@ -365,6 +396,90 @@ ray_adjoint_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restr
         pend = pend && !take;
         live = __ballot(pend);
     }
+}
+
+template <bool EXACT>
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_adjoint_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes, int nstart,
+                   const int *__restrict__ recv, int nrecv, const RayEntry *__restrict__ entries, int nentries,
+                   const double *__restrict__ w, int S, unsigned long long *__restrict__ acc,
+                   int *__restrict__ hits)
+{
+    ray_adjoint_body<EXACT>(G, v, boxes, entries, nentries, blockIdx.x * RAY_BLOCK + threadIdx.x, nstart * nrecv,
+                            [&](int r, int &s, int &q) { s = r / nrecv; q = recv[r - s * nrecv]; }, w, S, acc,
+                            hits);
+}
+
+template <bool EXACT>
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_pairs_adjoint_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes,
+                         const RayPair *__restrict__ pairs, int npair, const RayEntry *__restrict__ entries,
+                         int nentries, const double *__restrict__ w, int S, unsigned long long *__restrict__ acc,
+                         int *__restrict__ hits)
+{
+    ray_adjoint_body<EXACT>(G, v, boxes, entries, nentries, blockIdx.x * RAY_BLOCK + threadIdx.x, npair,
+                            [&](int r, int &s, int &q) { const RayPair pr = pairs[r]; s = pr.box; q = pr.recv; },
+                            w, S, acc, hits);
+}
+
+// The geometry of the ray of every pair, from the same walk.  Everything is kept in registers while the walk runs
+// and stored once it has returned its status: an INVALID ray is only known to be one when its walk fails.  Of the
+// first and the last hop the cells and d are kept; their offsets are decoded and their times read after the walk.
+template <bool EXACT>
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_pairs_geometry_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes,
+                          const RayPair *__restrict__ pairs, int npair, const RayEntry *__restrict__ entries,
+                          int nentries, int *__restrict__ status, RayGeometryOut O)
+{
+    const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
+    if (r >= npair) return;
+    const RayPair pr = pairs[r];
+    const RayBox B = boxes[pr.box];
+    const int q = pr.recv, nz = G.n[2], nyz = G.n[1] * G.n[2];
+    int hops = 0, first_p = q, last_c = q, deep = q, deepz = q % nz, end;
+    float d_first = 0.0f, d_last = 0.0f;
+    double length = 0.0;
+    const int st = ray_walk<EXACT>(G, v, B, entries, nentries, q, &end, [&](int c, int p, float d) {
+        if (hops == 0) {
+            first_p = p;
+            d_first = d;
+        }
+        hops++;
+        length = length + (double)d;
+        last_c = c;
+        d_last = d;
+        const int z = p % nz;       // FLOATBOX index (x * ny + y) * nz + z
+        if (z > deepz) {
+            deepz = z;
+            deep = p;
+        }
+    });
+    const bool ok = st == TTSWEEP_RAY_OK || st == TTSWEEP_RAY_SEED;
+    const bool hop = ok && hops > 0;
+    status[r] = st;
+    if (O.t_recv) O.t_recv[r] = B.T[q];
+    if (O.hops) O.hops[r] = ok ? hops : 0;
+    if (O.length) O.length[r] = ok ? length : 0.0;
+    if (O.deep) O.deep[r] = ok ? deep : -1;
+    // the hop out of the receiver, c = q -> p = first_p, and the hop into the end cell, c = last_c -> p = end
+    auto store = [&](int from, int to, float d, float dt, int *o3, float *od, float *odt) {
+        if (o3) {
+            const int fx = from / nyz, fy = (from - fx * nyz) / nz, fz = from - fx * nyz - fy * nz;
+            const int tx = to / nyz, ty = (to - tx * nyz) / nz, tz = to - tx * nyz - ty * nz;
+            o3[3 * (long long)r + 0] = hop ? tx - fx : 0;
+            o3[3 * (long long)r + 1] = hop ? ty - fy : 0;
+            o3[3 * (long long)r + 2] = hop ? tz - fz : 0;
+        }
+        if (od) od[r] = hop ? d : 0.0f;
+        if (odt) odt[r] = hop ? dt : 0.0f;
+    };
+    float dt_first = 0.0f, dt_last = 0.0f;
+    if (hop) {
+        dt_first = B.T[q] - B.T[first_p];
+        dt_last = B.T[last_c] - B.T[end];
+    }
+    store(q, first_p, d_first, dt_first, O.recv_hop, O.recv_d, O.recv_dt);
+    store(end, last_c, d_last, dt_last, O.src_hop, O.src_d, O.src_dt);
 }
 
 // The weights' scan: out[0] = max over nonzero w of (frexp exponent + 2048) (0: every weight is zero), out[1] =
@@ -436,6 +551,42 @@ hipError_t launch_ray_adjoint(const RayGeom &G, const float *v, const RayBox *bo
     auto kernel = exact ? ray_adjoint_kernel<true> : ray_adjoint_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, nstart, recv, nrecv, entries,
                        nentries, w, S, (unsigned long long *)acc, hits);
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_pairs_forward(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
+                                    int npair, const RayEntry *entries, int nentries, bool exact, const double *m,
+                                    double *y, int *status, hipStream_t st)
+{
+    if (npair <= 0) return hipSuccess;
+    const unsigned nblocks = (unsigned)(((long long)npair + RAY_BLOCK - 1) / RAY_BLOCK);
+    auto kernel = exact ? ray_pairs_forward_kernel<true> : ray_pairs_forward_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, pairs, npair, entries, nentries,
+                       m, y, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_pairs_adjoint(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
+                                    int npair, const RayEntry *entries, int nentries, bool exact, const double *w,
+                                    int S, long long *acc, int *hits, hipStream_t st)
+{
+    if (npair <= 0) return hipSuccess;
+    const unsigned nblocks = (unsigned)(((long long)npair + RAY_BLOCK - 1) / RAY_BLOCK);
+    auto kernel = exact ? ray_pairs_adjoint_kernel<true> : ray_pairs_adjoint_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, pairs, npair, entries, nentries,
+                       w, S, (unsigned long long *)acc, hits);
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_pairs_geometry(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
+                                     int npair, const RayEntry *entries, int nentries, bool exact, int *status,
+                                     const RayGeometryOut &out, hipStream_t st)
+{
+    if (npair <= 0) return hipSuccess;
+    const unsigned nblocks = (unsigned)(((long long)npair + RAY_BLOCK - 1) / RAY_BLOCK);
+    auto kernel = exact ? ray_pairs_geometry_kernel<true> : ray_pairs_geometry_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, pairs, npair, entries, nentries,
+                       status, out);
     return hipGetLastError();
 }
 

@@ -228,11 +228,51 @@ class TravelTimeSolver:
             _require(call(cells.data_ptr(), hop_d.data_ptr(), total) == total, "ray count changed between calls")
         return Rays(offsets, cells, hop_d, status, t_recv)
 
-    def frechet_operator(self, starts, tt, receivers, pred=None) -> "FrechetOperator":
+    def frechet_operator(self, starts, tt, receivers=None, pred=None, *, pairs=None) -> "FrechetOperator":
         """The Frechet matrix G of the rays from every start of tt to every receiver, as an operator
         (ttsweep_ray_forward_device / ttsweep_ray_adjoint_device): G m and G^T w without storing a path.
-        pred: the result of predecessors() for these boxes (computed once here when None)."""
-        return FrechetOperator(self, starts, tt, receivers, pred)
+        pred: the result of predecessors() for these boxes (computed once here when None).
+        pairs = (pair_box [npair], pair_recv [npair, 3]) instead of receivers: row r is the ray of box pair_box[r]
+        from the cell pair_recv[r] (ttsweep_ray_pairs_forward_device / ttsweep_ray_pairs_adjoint_device)."""
+        _require((receivers is None) != (pairs is None), "frechet_operator: give receivers or pairs")
+        return FrechetOperator(self, starts, tt, receivers, pred, pairs=pairs)
+
+    @staticmethod
+    def _pair_arrays(pair_box, pair_recv):
+        box = np.ascontiguousarray(np.asarray(pair_box, dtype=np.int32).reshape(-1))
+        recv = TravelTimeSolver._starts_array(pair_recv)
+        _require(len(box) == len(recv), f"pairs: {len(box)} boxes, {len(recv)} receivers")
+        return (C.c_int * max(len(box), 1)).from_buffer_copy(box.tobytes() if len(box) else bytes(4)), recv
+
+    def ray_geometry(self, starts, tt, pair_box, pair_recv, pred=None) -> "RayGeometry":
+        """ttsweep_ray_pairs_geometry_device: hop count, length, first and last hop and deepest cell of the ray of
+        box pair_box[r] from the cell pair_recv[r], for every pair, without storing a path.  pred: the result of
+        predecessors() for these boxes (computed when None)."""
+        import torch
+        arr = self._starts_array(starts)
+        n = len(arr)
+        self._require_device_tensor(tt, (n,) + self.shape, "travel-time boxes")
+        if pred is None:
+            pred = self.predecessors(starts, tt)
+        _require(isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_contiguous()
+                 and tuple(pred.shape) == tuple(tt.shape) and pred.device == tt.device,
+                 "pred: contiguous int32 tensor of the boxes' shape on their device")
+        box, recv = self._pair_arrays(pair_box, pair_recv)
+        npair = len(recv)
+        dev = tt.device
+        new = lambda dtype, *shape: torch.empty((npair,) + shape, dtype=dtype, device=dev)
+        out = RayGeometry(
+            status=torch.empty(npair, dtype=torch.int32), t_recv=new(torch.float32), hops=new(torch.int32),
+            length=new(torch.float64), recv_hop=new(torch.int32, 3), recv_d=new(torch.float32),
+            recv_dt=new(torch.float32), src_hop=new(torch.int32, 3), src_d=new(torch.float32),
+            src_dt=new(torch.float32), deep=new(torch.int32))
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.ttsweep_ray_pairs_geometry_device(
+            self._ctx, n, arr, self._box_pointers(tt, n), self._box_pointers(pred, n), npair, box, recv,
+            out.status.data_ptr(), out.t_recv.data_ptr(), out.hops.data_ptr(), out.length.data_ptr(),
+            out.recv_hop.data_ptr(), out.recv_d.data_ptr(), out.recv_dt.data_ptr(), out.src_hop.data_ptr(),
+            out.src_d.data_ptr(), out.src_dt.data_ptr(), out.deep.data_ptr()), "ttsweep_ray_pairs_geometry_device")
+        return out
 
     # -- event location -----------------------------------------------------
     def locate(self, tt, picks, weights=None, misfit_events=None) -> "Locations":
@@ -483,6 +523,73 @@ class Rays:
 
 
 @dataclass
+class RayGeometry:
+    """Geometry of the rays of TravelTimeSolver.ray_geometry (include/ttsweep.h, "rays: pair lists"), one row per
+    (box, receiver) pair; hops run in walk order, receiver -> source.  status is on the host, the rest on the device.
+      status   [npair] int32: RAY_OK / RAY_SEED / RAY_UNREACHED / RAY_INVALID
+      t_recv   [npair] float32: the travel time at the receiver
+      hops     [npair] int32: hops of the path; 0 for an UNREACHED or INVALID ray
+      length   [npair] float64: the sum of the hops' star lengths d
+      recv_hop [npair,3] int32, recv_d, recv_dt [npair] float32: offset, d and time difference of the hop out of the
+               receiver (pointing towards the source)
+      src_hop  [npair,3] int32, src_d, src_dt [npair] float32: the same of the hop out of the source
+      deep     [npair] int32: FLOATBOX index of the path cell with the greatest z, -1 for an UNREACHED or INVALID ray"""
+    status: "object"
+    t_recv: "object"
+    hops: "object"
+    length: "object"
+    recv_hop: "object"
+    recv_d: "object"
+    recv_dt: "object"
+    src_hop: "object"
+    src_d: "object"
+    src_dt: "object"
+    deep: "object"
+
+    def __len__(self):
+        return len(self.status)
+
+    def receiver_gradient(self):
+        """float64 [npair, 3]: (double)recv_dt * recv_hop[a] / (recv_hop . recv_hop), the travel time gained per cell
+        moved away from the source along axis a at the receiver (minus the slope of T along the first hop: the
+        partials of a hypocentre at the receiver cell); 0 for a ray without a hop."""
+        import torch
+        h = self.recv_hop.to(torch.float64)
+        n2 = (h * h).sum(dim=1, keepdim=True)
+        g = self.recv_dt.to(torch.float64)[:, None] * h / n2
+        return torch.where(n2 > 0, g, torch.zeros_like(g))
+
+    def takeoff(self):
+        """float64 [npair, 3]: the unit vector of src_hop, the direction in which the ray leaves the source, in
+        cells; 0 for a ray without a hop."""
+        import torch
+        h = self.src_hop.to(torch.float64)
+        n2 = (h * h).sum(dim=1, keepdim=True)
+        u = h / torch.sqrt(n2)
+        return torch.where(n2 > 0, u, torch.zeros_like(u))
+
+
+def pairs_from_locations(cells, weights=None, nstations=None):
+    """The (box, receiver) pairs of located events for TravelTimeSolver.frechet_operator(pairs=...) and
+    ray_geometry: the pair (k, cell[e]) of every (e, k) with weights[e][k] != 0 and an event cell, in (e, k) order.
+    cells: a Locations, or [E, 3] integer cells (x, y, z) with a negative row for an event without a cell.  weights:
+    [E, K] numpy or torch, None: every one of nstations stations is picked.  Returns numpy arrays
+    (pair_box int32 [npair], pair_recv int32 [npair, 3], event_of_pair int64, station_of_pair int64): with them the
+    residuals o[event_of_pair, station_of_pair] - t0[event_of_pair] - t_recv line up with the operator's rows."""
+    xyz = np.asarray(_host(cells.xyz if isinstance(cells, Locations) else cells)).reshape(-1, 3)
+    if weights is None:
+        _require(nstations is not None, "pairs_from_locations: weights or nstations")
+        picked = np.ones((len(xyz), int(nstations)), dtype=bool)
+    else:
+        picked = np.asarray(_host(weights)) != 0
+        _require(picked.ndim == 2 and len(picked) == len(xyz), "pairs_from_locations: weights [E, K], cells [E, 3]")
+    picked = picked & np.all(xyz >= 0, axis=1)[:, None]
+    event, station = np.nonzero(picked)         # row-major: (e, k) order
+    return (station.astype(np.int32), np.ascontiguousarray(xyz[event], dtype=np.int32), event.astype(np.int64),
+            station.astype(np.int64))
+
+
+@dataclass
 class Locations:
     """Events located by TravelTimeSolver.locate (include/ttsweep.h, "locate"), E events.
       cell    [E] int32 (device): FLOATBOX index of the best cell, -1 when no cell is admissible
@@ -584,12 +691,12 @@ class FrechetOperator:
     """G [nrays, nx*ny*nz] of TravelTimeSolver.trace_rays + rays_to_frechet, applied by walking the rays on the
     device instead of storing them (TravelTimeSolver.frechet_operator).  Holds the solver, the boxes, pred and
     the start and receiver lists as C arrays (built once); the boxes and pred must not change while it is used.
-      shape      (nrays, ncells); ray r = s * nrecv + q
+      shape      (nrays, ncells); ray r = s * nrecv + q, or pair r of a pair list
       status     [nrays] int32 (host): RAY_OK / RAY_SEED / RAY_UNREACHED / RAY_INVALID
       t_recv     [nrays] float32 (host): the travel time at the receiver
       last_scale S of the last rmatvec: g is summed in units of 2^-S (include/ttsweep.h)"""
 
-    def __init__(self, solver, starts, tt, receivers, pred=None):
+    def __init__(self, solver, starts, tt, receivers, pred=None, pairs=None):
         import torch
         self._sol = solver
         self._starts = solver._starts_array(starts)
@@ -600,19 +707,36 @@ class FrechetOperator:
         _require(isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_contiguous()
                  and tuple(pred.shape) == tuple(tt.shape) and pred.device == tt.device,
                  "pred: contiguous int32 tensor of the boxes' shape on their device")
-        self._recv = solver._starts_array(receivers)
         self.tt, self.pred = tt, pred
         self._tptr, self._pptr = solver._box_pointers(tt, n), solver._box_pointers(pred, n)
-        self._nstart, self._nrecv = n, len(self._recv)
         self.grid = solver.shape
-        self.shape = (n * len(self._recv), int(np.prod(solver.shape)))
         self.device = tt.device
         self.last_scale = 0
-        self.status = torch.empty(self.shape[0], dtype=torch.int32)
+        L = solver._L
+        if pairs is None:
+            self._recv = solver._starts_array(receivers)
+            nrays = n * len(self._recv)
+            self._rays = (n, self._starts, self._tptr, self._pptr, len(self._recv), self._recv)
+            self._calls = (L.ttsweep_ray_forward_device, "ttsweep_ray_forward_device",
+                           L.ttsweep_ray_adjoint_device, "ttsweep_ray_adjoint_device")
+        else:
+            self._pair_box, self._recv = solver._pair_arrays(*pairs)
+            nrays = len(self._recv)
+            self._rays = (n, self._starts, self._tptr, self._pptr, nrays, self._pair_box, self._recv)
+            self._calls = (L.ttsweep_ray_pairs_forward_device, "ttsweep_ray_pairs_forward_device",
+                           L.ttsweep_ray_pairs_adjoint_device, "ttsweep_ray_pairs_adjoint_device")
+        self._nstart = n
+        self.shape = (nrays, int(np.prod(solver.shape)))
+        self.status = torch.empty(nrays, dtype=torch.int32)
+        # the first forward call checks the rays (a box index or a receiver outside its range is refused there)
+        self._forward(torch.zeros(self.shape[1], dtype=torch.float64, device=self.device), self.status)
         recv = torch.from_numpy(np.frombuffer(self._recv, dtype=np.int32).reshape(-1, 3).astype(np.int64))
         flat = ((recv[:, 0] * self.grid[1] + recv[:, 1]) * self.grid[2] + recv[:, 2]).to(tt.device)
-        self.t_recv = tt.reshape(n, -1)[:, flat].reshape(-1).cpu()
-        self._forward(torch.zeros(self.shape[1], dtype=torch.float64, device=self.device), self.status)
+        if pairs is None:
+            self.t_recv = tt.reshape(n, -1)[:, flat].reshape(-1).cpu()
+        else:
+            box = torch.from_numpy(np.frombuffer(self._pair_box, dtype=np.int32)[:nrays].astype(np.int64))
+            self.t_recv = tt.reshape(n, -1)[box.to(tt.device), flat].cpu()
 
     def _cells(self, t, what):
         import torch
@@ -626,10 +750,8 @@ class FrechetOperator:
         import torch
         y = torch.empty(self.shape[0], dtype=torch.float64, device=self.device)
         torch.cuda.current_stream(self.device).synchronize()
-        _check(self._sol._L.ttsweep_ray_forward_device(
-            self._sol._ctx, self._nstart, self._starts, self._tptr, self._pptr, self._nrecv, self._recv,
-            m.data_ptr(), y.data_ptr(), None if status is None else status.data_ptr()),
-            "ttsweep_ray_forward_device")
+        _check(self._calls[0](self._sol._ctx, *self._rays, m.data_ptr(), y.data_ptr(),
+                              None if status is None else status.data_ptr()), self._calls[1])
         return y
 
     def matvec(self, m):
@@ -646,10 +768,9 @@ class FrechetOperator:
             w = w.contiguous()
             g = torch.empty(self.grid, dtype=torch.float64, device=self.device)
         torch.cuda.current_stream(self.device).synchronize()
-        _check(self._sol._L.ttsweep_ray_adjoint_device(
-            self._sol._ctx, self._nstart, self._starts, self._tptr, self._pptr, self._nrecv, self._recv,
-            None if w is None else w.data_ptr(), None if g is None else g.data_ptr(),
-            None if hits is None else hits.data_ptr(), C.byref(scale)), "ttsweep_ray_adjoint_device")
+        _check(self._calls[2](self._sol._ctx, *self._rays, None if w is None else w.data_ptr(),
+                              None if g is None else g.data_ptr(), None if hits is None else hits.data_ptr(),
+                              C.byref(scale)), self._calls[3])
         if w is not None:
             self.last_scale = scale.value
         return g
