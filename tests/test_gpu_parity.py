@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, assert_bit_equal
+from strip_cases import SCHEDULES
 
 pytestmark = pytest.mark.gpu
 
@@ -854,49 +855,6 @@ def test_result_does_not_depend_on_the_gate(P, golden24, speed, r0):
         assert sol.solve(starts, tts) == 1 and sol.stats()["kernel_variant"] == 2
     for k, tt in zip(keys, tts):
         assert_bit_equal(tt, golden24.z[f"tt_{k}"], f"{k} gate {speed}/{r0}")
-
-
-SCHEDULES = [
-    # (one launch per solve?, {option: value}) - every knob that decides WHEN a unit is relaxed or told
-    (1, {}),
-    (1, {"OPT_ASYNC_POLICY": 0}),
-    (1, {"OPT_ASYNC_POLICY": 0, "OPT_ASYNC_LOW": 1, "OPT_ASYNC_HIGH": 2}),
-    (1, {"OPT_ASYNC_POLICY": 1, "OPT_ASYNC_GATE_MILLI": 100, "OPT_ASYNC_LOW": 200, "OPT_ASYNC_HIGH": 4000}),
-    (1, {"OPT_ASYNC_POLICY": 1, "OPT_ASYNC_GATE_MILLI": 20000, "OPT_ASYNC_SPECIAL": 1}),
-    (1, {"OPT_ASYNC_POLICY": 2, "OPT_ASYNC_WINDOW_MILLI": 3000, "OPT_ASYNC_SPECIAL": 1 << 20}),
-    (1, {"OPT_ASYNC_POLICY": 2, "OPT_ASYNC_WINDOW_MILLI": 0}),
-    (1, {"OPT_DEFER_MARGIN_MILLI": -1000000000}),
-    (1, {"OPT_DEFER_MARGIN_MILLI": -4000}),
-    (1, {"OPT_DEFER_MARGIN_MILLI": 0, "OPT_GATE_SPEED_MILLI": 0}),
-    (1, {"OPT_DEFER_MARGIN_MILLI": 6000, "OPT_PAIR_MIN_STARTS": 0}),
-    (1, {"OPT_ASYNC_INUNIT": 0}),
-    (1, {"OPT_ASYNC_INUNIT": 1, "OPT_PAIR_MIN_STARTS": 0}),
-    (1, {"OPT_ASYNC_INUNIT": 8, "OPT_DEFER_MARGIN_MILLI": 1000}),
-    (1, {"OPT_ASYNC_INUNIT": 3, "OPT_PAIR_MIN_STARTS": 0, "OPT_ASYNC_POLICY": 0}),
-    # direct hand-off (round 5): workers publish successor units (1), their own unit (2), both; with every ring policy
-    # that allows it, a tiny ring fill, no gate, eager deferral, in-unit passes, one- and two-plane units
-    (1, {"OPT_ASYNC_HANDOFF": 1}),
-    (1, {"OPT_ASYNC_HANDOFF": 2}),
-    (1, {"OPT_ASYNC_HANDOFF": 3}),
-    (1, {"OPT_ASYNC_HANDOFF": 3, "OPT_PAIR_MIN_STARTS": 0}),
-    (1, {"OPT_ASYNC_HANDOFF": 3, "OPT_ASYNC_POLICY": 0, "OPT_ASYNC_LOW": 1, "OPT_ASYNC_HIGH": 2}),
-    (1, {"OPT_ASYNC_HANDOFF": 3, "OPT_GATE_SPEED_MILLI": 0, "OPT_DEFER_MARGIN_MILLI": -4000}),
-    (1, {"OPT_ASYNC_HANDOFF": 1, "OPT_ASYNC_GATE_MILLI": 100, "OPT_ASYNC_GATE_FAST_MILLI": 100, "OPT_ASYNC_INUNIT": 2}),
-    (1, {"OPT_ASYNC_HANDOFF": 3, "OPT_ASYNC_SPECIAL": 1, "OPT_DEFER_MARGIN_MILLI": -1000000000, "OPT_QUEUES": 1}),
-    (1, {"OPT_ASYNC_HANDOFF": 3, "OPT_ASYNC_POLICY": 2, "OPT_ASYNC_WINDOW_MILLI": 3000}),     # (policy 2: hand-off stays off)
-    # the latency instance (round 5): a unit relaxed by eight waves, four slabs in flight (one-plane units only: with
-    # units of two planes the option is ignored)
-    (1, {"OPT_ASYNC_WAVES": 8}),
-    (1, {"OPT_ASYNC_WAVES": 8, "OPT_ASYNC_INUNIT": 2}),
-    (1, {"OPT_ASYNC_WAVES": 8, "OPT_ASYNC_HANDOFF": 3, "OPT_ASYNC_INUNIT": 3, "OPT_DEFER_MARGIN_MILLI": 0}),
-    (1, {"OPT_ASYNC_WAVES": 8, "OPT_ASYNC_POLICY": 0, "OPT_ASYNC_LOW": 1, "OPT_ASYNC_HIGH": 2, "OPT_ASYNC_SPECIAL": 1}),
-    (1, {"OPT_ASYNC_WAVES": 8, "OPT_PAIR_MIN_STARTS": 0}),
-    (1, {"OPT_ASYNC_WAVES": 4, "OPT_PAIR_MIN_STARTS": 1000000}),
-    (0, {"OPT_DEFER_MARGIN_MILLI": -1000000000}),
-    (0, {"OPT_DEFER_MARGIN_MILLI": -4000}),
-    (0, {"OPT_DEFER_MARGIN_MILLI": 0, "OPT_PAIR_MIN_STARTS": 0}),
-    (0, {"OPT_DEFER_MARGIN_MILLI": 3000, "OPT_GATE_SPEED_MILLI": 700}),
-]
 
 
 @pytest.mark.parametrize("one_launch,options", SCHEDULES, ids=[f"{a}-{'-'.join(f'{k[4:]}={v}' for k, v in o.items()) or 'defaults'}"
