@@ -71,6 +71,8 @@ __device__ __forceinline__ float edge_delay(float h, float d, float sum)
 // Per-start device record.
 struct StartDesc {
     float *T;               // padded travel-time volume of this start
+    float *U;               // the caller's box (FLOATBOX layout, device memory) while it is kept in step with T - the
+                            // one-launch STRIP solve stores every improved cell into both -, or nullptr
     long long sidx;         // padded linear index of the start cell
     int sa, sb, sc;         // start cell, device-axis interior coordinates
     int pad_;

@@ -2,6 +2,7 @@
 // break (:168-169), i.e. old/sweep-serial/sweep-tt-multistart.c:189-211, on device-resident
 // boxes: passes of the kernel variant in use, enqueued one ahead of the convergence test.
 #include "ttsweep_ctx.h"
+#include "strip_rules.h"
 
 #include <algorithm>
 #include <chrono>
@@ -649,11 +650,18 @@ int solve_device_body(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
     ctx->np = np;
     const bool column = use_column(ctx, nstart);
     bool in_place = column && column_in_place(ctx, nstart, tt_dev);    // TILE, column driver: the caller's arrays ARE the volumes
+    // STRIP: fresh boxes are initialised in one launch for all starts (further down)
+    const bool batched = init && ctx->kernel == TTSWEEP_KERNEL_STRIP && L.cells % 4 == 0 && nstart <= 65535;
+    // STRIP: the caller's boxes equal the padded volumes when the solve is launched; the one-launch solve then keeps
+    // them equal (StartDesc::U) and nothing has to be copied back after it
+    const bool in_step = user_boxes_in_step(ctx->kernel == TTSWEEP_KERNEL_STRIP, L.perm[1] == 2, init != 0, batched, tt_dev, nstart);
+    bool one_launch_at_rest = false;
 
     for (int s = 0; s < nstart; s++) {
         const int u[3] = {starts[s].i, starts[s].j, starts[s].k};
         StartDesc &sd = ctx->h_starts[s];
         sd.T = ctx->d_T + (size_t)s * L.cells;
+        sd.U = in_step ? tt_dev[s] : nullptr;
         sd.sa = u[L.perm[0]];
         sd.sb = u[L.perm[1]];
         sd.sc = u[L.perm[2]];
@@ -667,8 +675,6 @@ int solve_device_body(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
         }
         sd.tile_flags = ctx->d_tile_flags + (size_t)s * flag_words(L, ctx->kernel);
         sd.work = ctx->d_work + 3 * s;
-        // (STRIP, fresh boxes: one launch for all starts further down)
-        const bool batched = init && ctx->kernel == TTSWEEP_KERNEL_STRIP && L.cells % 4 == 0 && nstart <= 65535;
         if (batched) { ctx->h_active[s] = s; continue; }
         if (in_place) {
             // (a fresh box is initialised where it lies: the reference's state, serial_new/...:139-144)
@@ -702,7 +708,7 @@ int solve_device_body(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
     }
     HIPCHK(hipMemcpyAsync(ctx->d_starts, ctx->h_starts, nstart * sizeof(StartDesc),
                           hipMemcpyHostToDevice, ctx->stream));
-    if (init && ctx->kernel == TTSWEEP_KERNEL_STRIP && L.cells % 4 == 0 && nstart <= 65535) {
+    if (batched) {      // (the padded volumes and, where StartDesc::U is set, the caller's boxes)
         HIPCHK(launch_init_tt_batch(L, ctx->d_T, ctx->d_starts, nstart, ctx->stream));
         HIPCHK(launch_init_tile_flags_batch(L, ctx->d_tile_flags, (long long)flag_words(L, ctx->kernel), ctx->d_starts, nstart,
                                             ctx->plans[np - 1].ra, np, ctx->stream));
@@ -789,6 +795,7 @@ int solve_device_body(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
             if (rc < 0) return rc;
             anychange_ever = rc > 0;
             nactive = 0;
+            one_launch_at_rest = true;
         }
         // (also when the launch gave up: what it had improved by then stays improved)
         for (int s = 0; s < nstart; s++) ctx->batch_changed[s] |= (ctx->h_changed[s] & CHANGED_IMPROVED) != 0;
@@ -890,6 +897,10 @@ int solve_device_body(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
 
     if (in_place) {
         // (the travel times were relaxed in the caller's arrays)
+    } else if (unpack_can_be_skipped(in_step, one_launch_at_rest, fell_back)) {
+        // (STRIP, one launch per solve: every store of a unit went into the caller's boxes as well; the few dead-edge
+        // cells are copied)
+        if (ctx->max_box_cells > 0) HIPCHK(launch_unpack_boxes(L, ctx->d_starts, nstart, ctx->stream));
     } else if (ctx->kernel == TTSWEEP_KERNEL_STRIP && nstart <= 65535 && nstart > 1) {
         // (all boxes in one launch; the boxes' addresses go through the pinned copy of the "changed" words,
         // which the driver loop is done with: PASS_SLOTS + 1 ints per start hold a pointer per start)

@@ -21,6 +21,8 @@ hipError_t launch_init_tt(const DevLayout &L, float *padded, long long sidx,
 // cell starts[s].sidx; users[s] = device address of box s (a device array)
 hipError_t launch_init_tt_batch(const DevLayout &L, float *T0, const StartDesc *starts, int nstart, hipStream_t st);
 hipError_t launch_unpack_batch(const DevLayout &L, const float *padded0, float *const *users, int nstart, hipStream_t st);
+// the cells of every start's dead-edge box, padded volume -> the caller's box starts[s].U (where it is set)
+hipError_t launch_unpack_boxes(const DevLayout &L, const StartDesc *starts, int nstart, hipStream_t st);
 
 // ---- device census / input check -------------------------------------------
 // *seen |= 1 << (XCD id) for every workgroup of an `nblocks`-workgroup launch

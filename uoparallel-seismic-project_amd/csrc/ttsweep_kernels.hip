@@ -52,6 +52,12 @@ __device__ __forceinline__ long long user_index(const DevLayout &L, int a, int b
     return ((long long)u[0] * L.un[1] + u[1]) * L.un[2] + u[2];
 }
 
+// ... and what one step along device axis d adds to it
+__device__ __forceinline__ long long user_stride(const DevLayout &L, int d)
+{
+    return L.perm[d] == 0 ? (long long)L.un[1] * L.un[2] : L.perm[d] == 1 ? (long long)L.un[2] : 1ll;
+}
+
 __global__ void __launch_bounds__(256)
 pack_kernel(DevLayout L, const float *__restrict__ user, float *__restrict__ padded,
             float halo_value)
@@ -111,16 +117,35 @@ unpack_rows_kernel(DevLayout L, const float *__restrict__ padded, float *__restr
 
 // The same for every start of a solve in ONE launch (blockIdx.y = start): a launch per start and kernel
 // was 1.2 ms of small, serialised kernels around the 24-start solve.
+// Where a start's descriptor names the caller's box (StartDesc::U), the box gets the same state: its cells are fewer
+// than the padded volume's, so the threads of the first float4s write one float4 of it as well - those that lie
+// on a 16-byte boundary of the box's address, which need not be aligned itself; the box's first and last cells go
+// one by one.
 __global__ void __launch_bounds__(256)
-init_tt_batch_kernel(long long cells, float *__restrict__ T0, const StartDesc *__restrict__ starts)
+init_tt_batch_kernel(DevLayout L, float *__restrict__ T0, const StartDesc *__restrict__ starts)
 {
     const long long idx4 = (long long)blockIdx.x * 256 + threadIdx.x;     // float4 of a padded volume
-    if (4 * idx4 >= cells) return;
-    const long long sidx = starts[blockIdx.y].sidx;
+    if (4 * idx4 >= L.cells) return;
+    const StartDesc *const sd = starts + blockIdx.y;
+    const long long sidx = sd->sidx;
     const float inf = __builtin_inff();
     float4 val = make_float4(inf, inf, inf, inf);
     if ((sidx >> 2) == idx4) reinterpret_cast<float *>(&val)[sidx & 3] = 0.0f;
-    reinterpret_cast<float4 *>(T0 + (long long)blockIdx.y * cells)[idx4] = val;
+    reinterpret_cast<float4 *>(T0 + (long long)blockIdx.y * L.cells)[idx4] = val;
+    float *const U = sd->U;
+    if (!U) return;
+    const long long ucells = (long long)L.un[0] * L.un[1] * L.un[2];
+    const long long uidx = user_index(L, sd->sa, sd->sb, sd->sc);
+    const long long first = 4 * idx4 - (long long)((reinterpret_cast<uintptr_t>(U) >> 2) & 3u);    // (U + first: 16-byte aligned)
+    if (first >= ucells) return;
+    float4 uval = make_float4(inf, inf, inf, inf);
+    if (uidx >= first && uidx < first + 4) reinterpret_cast<float *>(&uval)[uidx - first] = 0.0f;
+    if (first >= 0 && first + 4 <= ucells) {
+        *reinterpret_cast<float4 *>(U + first) = uval;
+    } else {
+        for (int i = 0; i < 4; i++)
+            if (first + i >= 0 && first + i < ucells) U[first + i] = reinterpret_cast<float *>(&uval)[i];
+    }
 }
 
 __global__ void __launch_bounds__(256)
@@ -133,12 +158,36 @@ unpack_batch_kernel(DevLayout L, const float *__restrict__ padded0, float *const
     if (interior(L, a, b, c)) users[blockIdx.y][user_index(L, a, b, c)] = padded0[(long long)blockIdx.y * L.cells + idx];
 }
 
+// The dead-edge boxes (StartDesc::box_*) of the starts whose caller's box is kept in step by the unit kernel's second
+// store: those cells are stored by relax_special_cell into the padded volume only, and go to the caller's box here,
+// after the solve (blockIdx.x = start).
+__global__ void __launch_bounds__(64)
+unpack_boxes_kernel(DevLayout L, const StartDesc *__restrict__ starts)
+{
+    const StartDesc sd = starts[blockIdx.x];
+    const int ea = sd.box_hi[0] - sd.box_lo[0] + 1, eb = sd.box_hi[1] - sd.box_lo[1] + 1, ec = sd.box_hi[2] - sd.box_lo[2] + 1;
+    if (!sd.U || ea <= 0 || eb <= 0 || ec <= 0) return;
+    for (int cell = threadIdx.x; cell < ea * eb * ec; cell += 64) {
+        const int c = sd.box_lo[2] + cell % ec, b = sd.box_lo[1] + cell / ec % eb, a = sd.box_lo[0] + cell / (ec * eb);
+        sd.U[user_index(L, a, b, c)] = sd.T[dev_index(L, a, b, c)];
+    }
+}
+
+hipError_t launch_unpack_boxes(const DevLayout &L, const StartDesc *starts, int nstart, hipStream_t st)
+{
+    if (nstart <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(unpack_boxes_kernel, dim3(nstart), dim3(64), 0, st, L, starts);
+    return hipGetLastError();
+}
+
 static inline unsigned blocks_for(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 hipError_t launch_init_tt_batch(const DevLayout &L, float *T0, const StartDesc *starts, int nstart, hipStream_t st)
 {
     if (nstart <= 0 || L.cells % 4 != 0 || nstart > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(init_tt_batch_kernel, dim3(blocks_for(L.cells / 4, 256), nstart), dim3(256), 0, st, L.cells, T0, starts);
+    // (the caller's box, cut into float4s from an aligned address on, takes at most a float4 more than its cells)
+    if (((long long)L.un[0] * L.un[1] * L.un[2] + 3) / 4 + 1 > L.cells / 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(init_tt_batch_kernel, dim3(blocks_for(L.cells / 4, 256), nstart), dim3(256), 0, st, L, T0, starts);
     return hipGetLastError();
 }
 
@@ -1160,6 +1209,9 @@ __device__ __forceinline__ void relax_special_cell(const DevLayout &L, const flo
     for (int w = 32; w >= 1; w >>= 1) best = fminf(best, __shfl_xor(best, w));
     const bool better = best < told;        // (wave-uniform: `best` is the wave's minimum)
     if (lane == 0 && better) {
+        // (no second store into the caller's box here, unlike the unit epilogue: two entries for one start's dead-edge
+        // cells can be in flight at once, and their stores into two arrays need not land in the same order - the
+        // padded volume heals, the cells are relaxed once more at rest, a copy would not: unpack_boxes_kernel)
         if (ASYNC) __hip_atomic_store(&T[ci], best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (write-through)
         else T[ci] = best;
         atomicOr(&changed[s], CHANGED_IMPROVED);
@@ -1996,6 +2048,15 @@ sweep_units_kernel(DevLayout L, const float *__restrict__ v, const StartDesc *__
         // of the flag word: zone set Zc of a cell becomes Zc | Zc << 3 (LO) | Zc << 6 (HI)
         const int zb_lo = lane < rb, zb_hi = lane >= STRIP_TB - rb;
         float *const Trow = T + own + fin_plane * L.s0 + fin_q0;
+        // One launch per solve: the caller's box (StartDesc::U, when it held the padded volume's values at the launch)
+        // gets every store as well, so that no pass has to copy the volume back after the solve.  The host names the
+        // box only where b is the caller's stride-1 axis (user_boxes_in_step, strip_rules.h: the headline grid) - the
+        // lanes of such a store then hit consecutive floats -; the address is right in every layout.  Write-through
+        // like the store into the padded volume: the unit's next turn may run on another XCD, and two write-back L2s
+        // would send their values for one cell to memory in an order nobody decides; a write-through store has
+        // arrived (the wait below) before the unit can be handed out again.
+        float *const U = ASYNC ? sdp->U : nullptr;
+        const long long urow = ASYNC ? user_index(L, a, b, c0 + fin_q0) : 0ll, ustep = user_stride(L, 2);
 #pragma unroll
         for (int qq = 0; qq < CQ; qq++) {
             const int cq = fin_q0 + qq;
@@ -2004,8 +2065,10 @@ sweep_units_kernel(DevLayout L, const float *__restrict__ v, const StartDesc *__
             if (row_ok && c < L.n[2] && !special && best[qq] < told[qq]) {
                 // (one launch per solve: a write-through store - global_store ... sc1 -, so that no write-back of the
                 // XCD's L2 is needed before the bits are pushed, only the wait for the stores themselves)
-                if (ASYNC) __hip_atomic_store(&Trow[qq], best[qq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else Trow[qq] = best[qq];
+                if (ASYNC) {
+                    __hip_atomic_store(&Trow[qq], best[qq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (U) __hip_atomic_store(&U[urow + qq * ustep], best[qq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else Trow[qq] = best[qq];
                 const int zc = 1 | (cq < STRIP_CF - 1 ? 2 : 0) | (cq > K - STRIP_CF ? 4 : 0);
                 improved |= zc | (zb_lo ? zc << 3 : 0) | (zb_hi ? zc << 6 : 0);
             }
