@@ -564,6 +564,78 @@ int ttsweep_locate_confidence_device(ttsweep_ctx *ctx, int nbox, const float *co
                                      long long *count_dev, long long *sum_dev, long long *sum2_dev,
                                      int *lo_dev, int *hi_dev, double *t0_lo_dev, double *t0_hi_dev);
 
+/* ---- fresnel: fat-ray (first Fresnel volume) sensitivities over pairs of boxes ---- */
+/* With boxes from a SYMMETRIC star, T_b[x] is also the travel time from x to the start of box b (the reciprocity
+ * "locate" relies on), so T_a[x] + T_b[x] - T_a[start_b] is the detour of the path a -> x -> b over the fastest path:
+ * zero on the ray, growing away from it.  The cells whose detour is below tau form the fat ray of the pair, weighted by
+ * a linear taper.  THE ABI DOES NOT CHECK THAT THE STAR IS SYMMETRIC OR THAT THE BOXES ARE CONVERGED: the arithmetic
+ * below is defined for any float values, it only means a Fresnel volume under those two conditions.  No velocity is
+ * needed: ctx supplies the grid and the device only.  Arguments shared by the three calls:
+ *   nbox, starts : the start cell of every box (host, nbox entries)
+ *   tt_dev       : host array of nbox device pointers, float boxes in FLOATBOX layout, any float values
+ *   npair        : the number of pairs
+ *   pair_a, pair_b : host, int32, npair entries each in [0, nbox).  A pair may repeat, each occurrence counts; a == b
+ *                  is allowed
+ *   tau          : host, double, npair entries: the half-width of the volume in the boxes' time unit
+ *   lo, hi       : host, int32 [npair][3], the inclusive window of cells of every pair; both NULL: the whole grid.
+ *                  Cells outside a pair's window are not visited (phi = 0 there)
+ *   status       : host, npair entries (TTSWEEP_FRESNEL_*), may be NULL
+ * Per pair r with a = pair_a[r], b = pair_b[r]: t_ab = T_a[start_b], one float.  status[r] is TTSWEEP_FRESNEL_OK, or
+ * TTSWEEP_FRESNEL_UNREACHED when !(t_ab < +INFINITY) (INFINITY or a NaN); an UNREACHED pair has no cells.  The weight
+ * of cell x, every operation rounded on its own (no contraction):
+ *   A = (double)T_a[x], B = (double)T_b[x];  phi = 0 if !(A < +INFINITY) or !(B < +INFINITY)
+ *   delta = (A + B) - (double)t_ab
+ *   phi   = 1.0 - delta / tau[r];   phi = 1.0 if phi > 1.0;   phi = 0 if !(phi > 0.0)   (so also for a NaN)
+ * The clamp to 1 is needed: on converged boxes rounding leaves delta slightly negative on and beside the thin ray.
+ * Cells with phi = 0 contribute to no output.  With K_c = ceil(log2(nx*ny*nz)) (0 for one cell), K_p =
+ * ceil(log2(npair)) (0 for one pair) and E_m, E_w the largest frexp exponents of the nonzero entries of m and w, every
+ * sum below is an int64 sum that cannot overflow (a term is below 2^(61-K) and there are at most 2^K of them), and
+ * the box limits are integer minima and maxima: all outputs are bit-identical from call to call, whatever the launch,
+ * the batching or the order of the pairs.  g, hits and both scales do not depend on the order of the pairs; y, phi,
+ * count, the boxes, t_ab and status follow it.  Passing the bounding boxes of the volume call as windows (an empty
+ * pair with any valid one-cell window) changes no bit of any output.
+ * Refused before any output is touched (ttsweep_last_error names the pair where there is one): a NULL pointer where
+ * one is needed; nbox < 1; npair < 0; npair > INT32_MAX; lo without hi or hi without lo; grids of more than INT32_MAX
+ * cells; a start outside the grid; a NULL box pointer; a pair index outside [0, nbox); a tau that is NaN, infinite or
+ * <= 0; a window outside the grid or with lo > hi; a NaN or infinite m or w - that one is found on the device, before
+ * y or g is touched, as in ttsweep_ray_adjoint_device.  npair == 0 succeeds: g and hits are zeroed and the scale is 0.
+ * The calls change no box and no state of the context; they allocate nothing that grows with the grid (g and hits are
+ * the caller's).  All return 0, or < 0 with ttsweep_last_error set. */
+#define TTSWEEP_HAS_FRESNEL 1       /* the three calls below exist (TTSWEEP_ABI_VERSION stays 6) */
+#define TTSWEEP_FRESNEL_OK 0
+#define TTSWEEP_FRESNEL_UNREACHED 2 /* t_ab is INFINITY or a NaN: the pair has no cells */
+
+/* The volume of every pair.  Every *_dev output is on the device, one entry per pair (lo_dev, hi_dev: three int32 per
+ * pair); each may be NULL.                                                                       empty pair:
+ *   t_ab_dev  float   t_ab                                                                       (as it is)
+ *   count_dev int64   the number of cells with phi > 0                                           0
+ *   lo_dev, hi_dev    the bounding box of those cells, inclusive                  (nx, ny, nz), (-1, -1, -1)
+ *   phi_dev   double  Phi_r = ldexp((double)sum_x llrint(ldexp(phi_r(x), 60 - K_c)), -(60 - K_c))   0.0 */
+int ttsweep_fresnel_volume_device(ttsweep_ctx *ctx, int nbox, const ttsweep_start *starts, const float *const *tt_dev,
+                                  long long npair, const int *pair_a, const int *pair_b, const double *tau,
+                                  const int *lo, const int *hi, int *status, float *t_ab_dev, long long *count_dev,
+                                  int *lo_dev, int *hi_dev, double *phi_dev);
+
+/* y = F m with F[r, x] = phi_r(x).  m_dev: device, double, FLOATBOX layout.  y_dev: device, double, npair entries.
+ * S_m = 61 - E_m - K_c and y[r] = ldexp((double)sum_x llrint(ldexp(phi_r(x) * m[x], S_m)), -S_m).  Every m zero: y = 0
+ * and S_m = 0.  scale: host, S_m, may be NULL.  With m = 1.0 everywhere y is phi_dev of the volume call bit for bit
+ * (E_m = 1). */
+int ttsweep_fresnel_forward_device(ttsweep_ctx *ctx, int nbox, const ttsweep_start *starts, const float *const *tt_dev,
+                                   long long npair, const int *pair_a, const int *pair_b, const double *tau,
+                                   const int *lo, const int *hi, const double *m_dev, double *y_dev, int *status,
+                                   int *scale);
+
+/* g = F^T w and hit counts.  w_dev: device, double, npair entries.  g_dev: device, double, FLOATBOX layout, written
+ * (w_dev and g_dev both NULL: hit counts only; one without the other is refused unless npair == 0).  hits_dev:
+ * device, int32, FLOATBOX layout: the number of pairs with phi_r(x) > 0, may be NULL.  scale: host, S_w, may be NULL.
+ * S_w = 61 - E_w - K_p; the visit of cell x by pair r adds llrint(ldexp(w[r] * phi_r(x), S_w)) to an int64 accumulator,
+ * which is g_dev itself as in ttsweep_ray_adjoint_device; then g[x] = ldexp((double)acc[x], -S_w).  Every weight zero:
+ * g = 0 and S_w = 0. */
+int ttsweep_fresnel_adjoint_device(ttsweep_ctx *ctx, int nbox, const ttsweep_start *starts, const float *const *tt_dev,
+                                   long long npair, const int *pair_a, const int *pair_b, const double *tau,
+                                   const int *lo, const int *hi, const double *w_dev, double *g_dev, int *hits_dev,
+                                   int *status, int *scale);
+
 /* Multi-GPU form of ttsweep_solve for a host program: the start points are
  * independent (serial_new/...:158-162; mpi/backup.c:351-363 runs one start per
  * rank), so the starts are dealt over the devices, longest first by estimated cost

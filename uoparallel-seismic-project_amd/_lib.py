@@ -95,6 +95,12 @@ SYMBOLS = [
     ("ttsweep_locate_confidence_device", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ttsweep_fresnel_volume_device", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong]
+                                               + [C.c_void_p] * 11),
+    ("ttsweep_fresnel_forward_device", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong]
+                                                + [C.c_void_p] * 9),
+    ("ttsweep_fresnel_adjoint_device", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong]
+                                                + [C.c_void_p] * 10),
     ("ttsweep_solve_multi", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     ("ttsweep_solve_multi_changed", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -118,6 +124,7 @@ OPT_TILE_ORDER = 24
 KERNEL_AUTO, KERNEL_CELL, KERNEL_STRIP, KERNEL_TILE = 0, 1, 2, 3
 PRED_SOURCE, PRED_SEED, PRED_UNREACHED = -1, -2, -3
 RAY_OK, RAY_SEED, RAY_UNREACHED, RAY_INVALID = 0, 1, 2, 3
+FRESNEL_OK, FRESNEL_UNREACHED = 0, 2
 
 
 def build(verbose: bool = False) -> str:

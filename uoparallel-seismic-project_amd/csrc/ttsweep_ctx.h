@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <cstring>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -25,6 +26,36 @@ namespace ttsweep {
 
 // error text of the calling thread (ttsweep_last_error); returns -1
 int set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+
+// The device scratch of one call: add() declares the arrays, alloc() allocates them as one block, each aligned to 256
+// bytes, and sets the pointers in the order of their declaration
+class Scratch {
+    char *p = nullptr;
+    size_t bytes = 0;
+    std::vector<std::pair<void *, size_t>> slots;      // where a pointer is kept, and its offset
+
+public:
+    ~Scratch()
+    {
+        if (p) (void)hipFree(p);
+    }
+    template <typename T>
+    void add(T *&ptr, size_t n)
+    {
+        slots.push_back({&ptr, bytes});
+        bytes += (n * sizeof(T) + 255) & ~(size_t)255;
+    }
+    hipError_t alloc()
+    {
+        const hipError_t err = hipMalloc((void **)&p, bytes);
+        if (err != hipSuccess) return err;
+        for (const auto &s : slots) {
+            char *q = p + s.second;
+            memcpy(s.first, &q, sizeof(q));
+        }
+        return hipSuccess;
+    }
+};
 
 } // namespace ttsweep
 

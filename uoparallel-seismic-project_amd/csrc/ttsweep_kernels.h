@@ -299,6 +299,44 @@ hipError_t launch_confidence_final(long long n, const unsigned long long *g_sum,
                                    const int *g_box, long long *count, long long *sum, long long *sum2, int *lo,
                                    int *hi, double *t0_lo, double *t0_hi, hipStream_t st);
 
+// Fresnel volumes over box pairs (ttsweep_fresnel.hip).  Pair r reads box a (Ta) against box b (Tb) over its window
+// of wx * wy * wz cells from the FLOATBOX index x0 (cell lo).  A row of the window is cut into quads of 4 consecutive
+// z (the last one ragged): quad q = (cx * wy + cy) * ceil(wz / 4) + zq, nquad of them, cut into tiles of
+// fresnel_tile_quads().  first[r] is the number of tiles of the pairs before r (first[npair]: of all), so block b of
+// the call belongs to the pair r with first[r] <= b < first[r + 1] and is tile b - first[r] of it.
+struct FresPair {
+    const float *Ta, *Tb;
+    double tau;
+    int sb;                 // FLOATBOX index of box b's start cell
+    int x0;                 // FLOATBOX index of the window's lo corner
+    int lo[3];              // the window's lo corner, in cells
+    int wy, wz;             // cells of the window along y and z
+    int nquad;
+};
+int fresnel_tile_quads();
+// t_ab[r] = Ta[sb] and status[r] (TTSWEEP_FRESNEL_*) of every pair
+hipError_t launch_fresnel_pairs(const FresPair *pairs, int npair, float *t_ab, int *status, hipStream_t st);
+// the accumulators of the volume call at their empty-pair values: cnt, sum = 0, box [npair][6] = (nx, ny, nz, -1, -1, -1)
+hipError_t launch_fresnel_init(int npair, int nx, int ny, int nz, unsigned long long *cnt, unsigned long long *sum,
+                               int *box, hipStream_t st);
+// blocks [block0, block0 + nblocks) of the call.  volume: cnt[r] += cells with phi > 0, sum[r] += llrint(ldexp(phi,
+// S)), box[r] their bounding box; forward: sum[r] += llrint(ldexp(phi * m[x], S)); adjoint: acc[x] += llrint(ldexp(w[r]
+// * phi, S)) (w, acc both nullptr: none) and hits[x] += 1 (nullptr: none).  gnyz, gnz: ny * nz and nz of the grid.
+hipError_t launch_fresnel_volume(const FresPair *pairs, const long long *first, int npair, long long block0,
+                                 int nblocks, const float *t_ab, int gnyz, int gnz, int S, unsigned long long *cnt,
+                                 unsigned long long *sum, int *box, hipStream_t st);
+hipError_t launch_fresnel_forward(const FresPair *pairs, const long long *first, int npair, long long block0,
+                                  int nblocks, const float *t_ab, int gnyz, int gnz, int S, const double *m,
+                                  unsigned long long *sum, hipStream_t st);
+hipError_t launch_fresnel_adjoint(const FresPair *pairs, const long long *first, int npair, long long block0,
+                                  int nblocks, const float *t_ab, int gnyz, int gnz, int S, const double *w,
+                                  long long *acc, int *hits, hipStream_t st);
+// the accumulators to the caller's arrays (each may be nullptr): count / lo / hi as they are, out[r] = ldexp((double)
+// sum[r], -S) (phi of the volume call, y of the forward call)
+hipError_t launch_fresnel_final(int npair, int S, const unsigned long long *cnt, const unsigned long long *sum,
+                                const int *box, const float *t_ab, long long *count, int *lo, int *hi, double *out,
+                                float *t_ab_out, hipStream_t st);
+
 #ifdef TTSWEEP_TILE_PROFILE
 void tile_prof_dump();   // prints and clears the phase counters of tile_sweep_kernel
 #endif

@@ -1,11 +1,11 @@
 // ttsweep_locate.cpp - ttsweep_locate_device, ttsweep_locate_window_device, ttsweep_locate_subcell_device and
 // ttsweep_locate_confidence_device of include/ttsweep.h (kernels: ttsweep_locate.hip).  The four entry points are built
 // from the same pieces: the argument, window, grid and box-pointer checks (each refusal once; an entry point calls them
-// in the order in which its refusals take precedence, those that need no device first), one scratch carver, the check
-// scan of picks and weights (refused before any output is touched) and, for the searches over windows, one cut of the
-// groups into batches whose per-tile partials stay within a fixed budget and one driver of those batches.  The scratch
-// is allocated per call: nothing of the context changes, so the boxes the confirming-pass shortcut of ttsweep_solve
-// remembers, its pools and its options stay as they are.
+// in the order in which its refusals take precedence, those that need no device first), one scratch carver (Scratch,
+// ttsweep_ctx.h), the check scan of picks and weights (refused before any output is touched) and, for the searches over
+// windows, one cut of the groups into batches whose per-tile partials stay within a fixed budget and one driver of
+// those batches.  The scratch is allocated per call: nothing of the context changes, so the boxes the confirming-pass
+// shortcut of ttsweep_solve remembers, its pools and its options stay as they are.
 #include "ttsweep_ctx.h"
 
 #include <algorithm>
@@ -24,36 +24,6 @@ constexpr long long LOC_PARTIALS = 1LL << 24;
 // blocks (group, tile) of one batch of ttsweep_locate_window_device / ttsweep_locate_subcell_device, at most (8 bytes
 // each) (both mirrored: tests/test_gpu_locate_subcell.py::test_a_batch_edge)
 constexpr long long LOC_WIN_BLOCKS = 1LL << 22;
-
-// The device scratch of one call: add() declares the arrays, alloc() allocates them as one block, each aligned to 256
-// bytes, and sets the pointers in the order of their declaration
-class Scratch {
-    char *p = nullptr;
-    size_t bytes = 0;
-    std::vector<std::pair<void *, size_t>> slots;      // where a pointer is kept, and its offset
-
-public:
-    ~Scratch()
-    {
-        if (p) (void)hipFree(p);
-    }
-    template <typename T>
-    void add(T *&ptr, size_t n)
-    {
-        slots.push_back({&ptr, bytes});
-        bytes += (n * sizeof(T) + 255) & ~(size_t)255;
-    }
-    hipError_t alloc()
-    {
-        const hipError_t err = hipMalloc((void **)&p, bytes);
-        if (err != hipSuccess) return err;
-        for (const auto &s : slots) {
-            char *q = p + s.second;
-            memcpy(s.first, &q, sizeof(q));
-        }
-        return hipSuccess;
-    }
-};
 
 int check_counts(const char *what, int nbox, int nevent, bool pointers)
 {

@@ -274,6 +274,56 @@ class TravelTimeSolver:
             out.src_d.data_ptr(), out.src_dt.data_ptr(), out.deep.data_ptr()), "ttsweep_ray_pairs_geometry_device")
         return out
 
+    # -- fat rays ------------------------------------------------------------
+    def _fresnel_args(self, starts, tt, pair_a, pair_b, tau, lo, hi):
+        """The shared arguments of the three ttsweep_fresnel_*_device calls as a tuple, checked; the arrays it points
+        into are kept alive by the tuple's last entry."""
+        arr = self._starts_array(starts)
+        n = len(arr)
+        _require(n >= 1, "fresnel: at least one box")
+        self._require_device_tensor(tt, (n,) + self.shape, "travel-time boxes")
+        a = np.ascontiguousarray(np.asarray(pair_a, dtype=np.int32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(pair_b, dtype=np.int32).reshape(-1))
+        npair = len(a)
+        _require(len(b) == npair, f"pairs: {npair} boxes a, {len(b)} boxes b")
+        _require(npair == 0 or (min(a.min(), b.min()) >= 0 and max(a.max(), b.max()) < n),
+                 f"pairs: box indices in [0, {n})")
+        tau = np.asarray(tau if isinstance(tau, (np.ndarray, list, tuple, float, int)) else _host(tau),
+                         dtype=np.float64)
+        _require(tau.shape in ((), (npair,)), f"tau: a number or [{npair}] values")
+        tau = np.ascontiguousarray(np.broadcast_to(tau, (npair,)))
+        lo, hi = self._windows(npair, lo, hi)
+        keep = (arr, a, b, tau, lo, hi, tt)
+        ptr = lambda x: None if x is None else x.ctypes.data
+        return (self._ctx, n, arr, self._box_pointers(tt, n), npair, ptr(a), ptr(b), ptr(tau), ptr(lo), ptr(hi), keep)
+
+    def fresnel_volumes(self, starts, tt, pair_a, pair_b, tau, lo=None, hi=None) -> "FresnelVolumes":
+        """ttsweep_fresnel_volume_device: the fat ray (first Fresnel volume) of every pair (box pair_a[r], box
+        pair_b[r]) of tt (torch float32 [nbox,nx,ny,nz] on this solver's device, box k solved from starts[k] with a
+        symmetric star): the cells whose detour T_a[x] + T_b[x] - T_a[start_b] is below tau[r] (a number or [npair]),
+        weighted by the linear taper phi (include/ttsweep.h, "fresnel").  lo, hi: inclusive windows, [3] or
+        [npair,3]; both None: the whole grid."""
+        import torch
+        args = self._fresnel_args(starts, tt, pair_a, pair_b, tau, lo, hi)
+        npair, dev = args[4], tt.device
+        new = lambda dtype, *shape: torch.empty((npair,) + shape, dtype=dtype, device=dev)
+        out = FresnelVolumes(status=torch.empty(npair, dtype=torch.int32), t_ab=new(torch.float32),
+                             count=new(torch.int64), phi=new(torch.float64), lo=new(torch.int32, 3),
+                             hi=new(torch.int32, 3),
+                             start_a=np.frombuffer(args[2], dtype=np.int32).reshape(-1, 3)[args[10][1]])
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.ttsweep_fresnel_volume_device(
+            *args[:10], out.status.data_ptr(), out.t_ab.data_ptr(), out.count.data_ptr(), out.lo.data_ptr(),
+            out.hi.data_ptr(), out.phi.data_ptr()), "ttsweep_fresnel_volume_device")
+        return out
+
+    def fresnel_operator(self, starts, tt, pair_a, pair_b, tau, norm=None, windows=True) -> "FresnelOperator":
+        """The fat-ray sensitivity matrix of the pairs as an operator for lsqr: row r is coef[r] * phi_r(x), coef =
+        norm / Phi (0 where Phi = 0; norm None: 1), so a row sums to norm[r] - with norm = ray_geometry(...).length
+        to the thin ray's length, the unit the rows of frechet_operator carry.  Built from one volume call; windows:
+        feed the volumes' bounding boxes back as windows (fewer cells visited, the same bits)."""
+        return FresnelOperator(self, starts, tt, pair_a, pair_b, tau, norm=norm, windows=windows)
+
     # -- event location -----------------------------------------------------
     def locate(self, tt, picks, weights=None, misfit_events=None) -> "Locations":
         """ttsweep_locate_device: grid-search location of events over station boxes (include/ttsweep.h, "locate").
@@ -787,6 +837,124 @@ class FrechetOperator:
 
     def hits(self):
         """int32 [nx,ny,nz]: the number of OK or SEED rays whose path holds each cell."""
+        import torch
+        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
+        self._adjoint(None, hits)
+        return hits
+
+
+@dataclass
+class FresnelVolumes:
+    """Volumes of TravelTimeSolver.fresnel_volumes (include/ttsweep.h, "fresnel"), one entry per pair.
+      status  [npair] int32 (host): FRESNEL_OK / FRESNEL_UNREACHED
+      t_ab    [npair] float32 (device): T_a at the start of box b
+      count   [npair] int64 (device): cells with phi > 0
+      phi     [npair] float64 (device): the sum of phi over them (int64 fixed point, deterministic)
+      lo, hi  [npair,3] int32 (device): their bounding box; (nx, ny, nz) and (-1, -1, -1) for an empty pair
+      start_a [npair,3] int32 (host): the start cell of box a of every pair"""
+    status: "object"
+    t_ab: "object"
+    count: "object"
+    phi: "object"
+    lo: "object"
+    hi: "object"
+    start_a: "object"
+
+    def __len__(self):
+        return len(self.status)
+
+    def windows(self):
+        """(lo, hi) int32 [npair,3] on the host, valid as windows of the fresnel calls: the bounding boxes, an empty
+        pair collapsed to the start cell of its box a."""
+        lo, hi = _host(self.lo).copy(), _host(self.hi).copy()
+        empty = _host(self.count) == 0
+        lo[empty] = hi[empty] = self.start_a[empty]
+        return lo, hi
+
+
+class FresnelOperator:
+    """F [npair, nx*ny*nz] with F[r, x] = coef[r] * phi_r(x), applied by streaming the two boxes of every pair on the
+    device (TravelTimeSolver.fresnel_operator); lsqr takes it as it is.  The boxes must not change while it is used.
+      shape      (npair, ncells)
+      status     [npair] int32 (host): FRESNEL_OK / FRESNEL_UNREACHED
+      volumes    the FresnelVolumes of the one volume call it was built from
+      coef       [npair] float64 (device): norm / Phi, 0 where Phi = 0
+      last_scale S_w of the last rmatvec, last_forward_scale S_m of the last matvec (include/ttsweep.h)"""
+
+    def __init__(self, solver, starts, tt, pair_a, pair_b, tau, norm=None, windows=True):
+        import torch
+        self._sol = solver
+        self.volumes = solver.fresnel_volumes(starts, tt, pair_a, pair_b, tau)
+        lo, hi = self.volumes.windows() if windows else (None, None)
+        self._args = solver._fresnel_args(starts, tt, pair_a, pair_b, tau, lo, hi)
+        npair = self._args[4]
+        self.tt, self.grid, self.device = tt, solver.shape, tt.device
+        self.shape = (npair, int(np.prod(solver.shape)))
+        self.status = self.volumes.status
+        phi = self.volumes.phi
+        if norm is None:
+            norm = torch.ones(npair, dtype=torch.float64, device=self.device)
+        elif not isinstance(norm, torch.Tensor):
+            norm = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(norm, dtype=np.float64), (npair,))))
+        norm = norm.to(device=self.device, dtype=torch.float64)
+        _require(tuple(norm.shape) == (npair,), f"norm: [{npair}] values")
+        self.coef = torch.where(phi > 0, norm / phi, torch.zeros_like(phi))
+        self.last_scale = 0
+        self.last_forward_scale = 0
+
+    def _cells(self, t, what):
+        import torch
+        _require(isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == self.device,
+                 f"{what}: float64 tensor on {self.device}")
+        _require(t.numel() == self.shape[1] and tuple(t.shape) in ((self.shape[1],), self.grid),
+                 f"{what}: shape {tuple(t.shape)}, want {self.grid} or ({self.shape[1]},)")
+        return t.contiguous()
+
+    def forward_raw(self, m):
+        """y = F m without the row coefficients: ttsweep_fresnel_forward_device as it is."""
+        import torch
+        m = self._cells(m, "m")
+        y = torch.empty(self.shape[0], dtype=torch.float64, device=self.device)
+        scale = C.c_int(0)
+        torch.cuda.current_stream(self.device).synchronize()
+        _check(self._sol._L.ttsweep_fresnel_forward_device(*self._args[:10], m.data_ptr(), y.data_ptr(), None,
+                                                           C.byref(scale)), "ttsweep_fresnel_forward_device")
+        self.last_forward_scale = scale.value
+        return y
+
+    def matvec(self, m):
+        """coef * (F m): m float64 [nx,ny,nz] or [ncells] on the device; float64 [npair]."""
+        return self.coef * self.forward_raw(m)
+
+    def _adjoint(self, w, hits):
+        import torch
+        scale = C.c_int(0)
+        g = None
+        if w is not None:
+            _require(isinstance(w, torch.Tensor) and w.dtype == torch.float64 and w.device == self.device
+                     and tuple(w.shape) == (self.shape[0],), f"w: float64 [{self.shape[0]}] on {self.device}")
+            w = (self.coef * w).contiguous()
+            g = torch.empty(self.grid, dtype=torch.float64, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        _check(self._sol._L.ttsweep_fresnel_adjoint_device(
+            *self._args[:10], None if w is None else w.data_ptr(), None if g is None else g.data_ptr(),
+            None if hits is None else hits.data_ptr(), None, C.byref(scale)), "ttsweep_fresnel_adjoint_device")
+        if w is not None:
+            self.last_scale = scale.value
+        return g
+
+    def rmatvec(self, w):
+        """F^T (coef * w): w float64 [npair] on the device; float64 [nx,ny,nz], deterministic (int64 fixed point)."""
+        return self._adjoint(w, None)
+
+    def rmatvec_hits(self, w):
+        """(F^T (coef * w), hits) of one pass."""
+        import torch
+        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
+        return self._adjoint(w, hits), hits
+
+    def hits(self):
+        """int32 [nx,ny,nz]: the number of pairs whose volume holds each cell."""
         import torch
         hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
         self._adjoint(None, hits)
