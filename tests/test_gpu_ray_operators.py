@@ -243,6 +243,137 @@ def test_bad_operator_calls_are_refused(P):
             sol.frechet_operator([start], t, [[0, 0, g.v.shape[2]]])
 
 
+def test_dense_refusals_leave_the_outputs_untouched(P):
+    """The dense calls (forward, adjoint, trace) through the C ABI on the g9 grid with four starts, as
+    test_refusals_leave_the_outputs_untouched of test_gpu_ray_pairs.py pins the pair calls: every output is filled
+    with -7 and is still -7 after each refusal, the message names the function and the argument; then the accepted
+    edge cases."""
+    import ctypes as C
+    import torch
+    g = Golden("g9")
+    v = g.v
+    fs = P.inputs.make_fs(g.star("818"))
+    starts = np.array([[4, 3, 2], [0, 0, 0], [8, 6, 4], [2, 5, 1]], np.int32)
+    recv = np.array([[1, 1, 1], [2, 2, 2], [3, 3, 3], [4, 4, 4], [5, 5, 4], [8, 6, 4]], np.int32)
+    n, nrecv, ncells = len(starts), len(recv), v.size
+    nrays = n * nrecv
+    lib = P._lib.lib()
+    d = dev()
+    with solver_for(P, v, fs) as sol, P.TravelTimeSolver(v.shape, fs) as no_velocity:
+        tt = torch.empty((n,) + v.shape, dtype=torch.float32, device=d)
+        assert sol.solve_device(starts, tt, init=True) == 1
+        pred = sol.predecessors(starts, tt)
+        arr, tp, pp = sol._starts_array(starts), sol._box_pointers(tt, n), sol._box_pointers(pred, n)
+        rarr = sol._starts_array(recv)
+        sent = {
+            "y": torch.full((nrays,), -7.0, dtype=torch.float64, device=d),
+            "g": torch.full((ncells,), -7.0, dtype=torch.float64, device=d),
+            "hits": torch.full((ncells,), -7, dtype=torch.int32, device=d),
+            "status": torch.full((nrays,), -7, dtype=torch.int32),
+            "offsets": torch.full((nrays + 1,), -7, dtype=torch.int64),
+            "t_recv": torch.full((nrays,), -7.0, dtype=torch.float32),
+            "cells": torch.full((nrays * 16,), -7, dtype=torch.int32, device=d),
+            "hop_d": torch.full((nrays * 16,), -7.0, dtype=torch.float32, device=d),
+        }
+        mdev = torch.ones(ncells, dtype=torch.float64, device=d)
+        wdev = torch.ones(nrays, dtype=torch.float64, device=d)
+        scale = C.c_int(-7)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        torch.cuda.synchronize()
+
+        def untouched(*names):
+            torch.cuda.synchronize()
+            return all(bool(torch.all(sent[k] == -7)) for k in (names or sent)) and (bool(names) or scale.value == -7)
+
+        def reset():
+            for t in sent.values():
+                t.fill_(-7)
+            scale.value = -7
+            torch.cuda.synchronize()
+
+        def calls(ctx=sol._ctx, nstart=n, arr_=arr, tp_=tp, nrecv_=nrecv, rarr_=rarr, m=mdev, y=sent["y"], w=wdev,
+                  g_=sent["g"], offsets=sent["offsets"], capacity=nrays * 16):
+            head = (ctx, nstart, arr_, tp_, pp, nrecv_, rarr_)
+            return {
+                "ray_forward": lambda: lib.ttsweep_ray_forward_device(*head, ptr(m), ptr(y), ptr(sent["status"])),
+                "ray_adjoint": lambda: lib.ttsweep_ray_adjoint_device(*head, ptr(w), ptr(g_), ptr(sent["hits"]),
+                                                                      C.byref(scale)),
+                "trace_rays": lambda: lib.ttsweep_trace_rays_device(
+                    *head, ptr(offsets), ptr(sent["status"]), ptr(sent["t_recv"]), ptr(sent["cells"]),
+                    ptr(sent["hop_d"]), capacity),
+            }
+
+        def refused(message, only=("ray_forward", "ray_adjoint", "trace_rays"), **kw):
+            for name, call in calls(**kw).items():
+                if name not in only:
+                    continue
+                assert call() < 0, (name, message)
+                err = P._lib.last_error()
+                assert f"ttsweep_{name}_device" in err and message in err, (name, err)
+                assert untouched(), (name, message)
+
+        operators = ("ray_forward", "ray_adjoint")
+        refused("null or bad argument", nstart=-1)
+        refused("null or bad argument", nrecv_=-1)
+        refused("null or bad argument", rarr_=None)
+        refused("int32", only=operators, nstart=65536, nrecv_=65536)
+        hole = sol._box_pointers(tt, n)
+        hole[2] = None
+        refused("null box pointer 2", tp_=hole)
+        outside = sol._starts_array(np.concatenate([starts[:-1], [[0, v.shape[1], 0]]]))
+        refused("start 3 ", arr_=outside)
+        r2 = recv.copy()
+        r2[1] = [2, 2, v.shape[2]]
+        refused("receiver 1 ", rarr_=sol._starts_array(r2))
+        r2[1], r2[5] = [2, 2, 2], [-1, 0, 0]
+        refused("receiver 5 ", rarr_=sol._starts_array(r2))
+        refused("velocity not set", ctx=no_velocity._ctx)
+        refused("null or bad argument", only=("ray_forward",), m=None)
+        refused("null or bad argument", only=("ray_forward",), y=None)
+        refused("both", only=("ray_adjoint",), w=None)
+        refused("both", only=("ray_adjoint",), g_=None)
+        for badw in (float("nan"), float("inf")):
+            wb = wdev.clone()
+            wb[9] = badw
+            refused("NaN or infinite", only=("ray_adjoint",), w=wb)
+        refused("null or bad argument", only=("trace_rays",), offsets=None)
+        # precedence: a bad receiver together with a NULL m reports the receiver
+        refused("receiver 5 ", only=("ray_forward",), rarr_=sol._starts_array(r2), m=None)
+
+        # accepted: no starts or no receivers.  forward writes nothing; adjoint zeroes g and hits, S = 0; the trace
+        # sets offsets[0] = 0 and returns 0
+        for kw in ({"nstart": 0}, {"nrecv_": 0}, {"nrecv_": 0, "rarr_": None}):
+            for name, call in calls(**kw).items():
+                assert call() == 0, (name, kw, P._lib.last_error())
+            torch.cuda.synchronize()
+            assert untouched("y", "status", "t_recv", "cells", "hop_d"), kw
+            assert scale.value == 0 and not bool(torch.any(sent["g"] != 0)) and not bool(torch.any(sent["hits"] != 0))
+            assert sent["offsets"][0] == 0 and bool(torch.all(sent["offsets"][1:] == -7)), kw
+            reset()
+        # adjoint with g and hits both NULL: S = 0, nothing else
+        assert lib.ttsweep_ray_adjoint_device(sol._ctx, n, arr, tp, pp, nrecv, rarr, None, None, None,
+                                              C.byref(scale)) == 0
+        assert scale.value == 0 and untouched("y", "g", "hits", "status")
+        reset()
+        # a trace without room for the paths: the total, offsets, status and t_recv, and no cell
+        for capacity in (0, 1):
+            total = calls(capacity=capacity)["trace_rays"]()
+            assert total > nrays and total == int(sent["offsets"][-1]) and sent["offsets"][0] == 0
+            assert untouched("cells", "hop_d") and bool(torch.all(sent["status"] == P.RAY_OK))
+            assert not bool(torch.any(sent["t_recv"] == -7))
+            reset()
+        assert total <= nrays * 16
+        # the same arguments are accepted: every output is written
+        for name, call in calls().items():
+            assert call() == (total if name == "trace_rays" else 0), (name, P._lib.last_error())
+        torch.cuda.synchronize()
+        assert scale.value != -7
+        for k in ("y", "g", "hits", "status", "offsets", "t_recv"):
+            assert not bool(torch.any(sent[k] == -7)), k
+        assert not bool(torch.any(sent["cells"][:total] == -7)) and not bool(torch.any(sent["hop_d"][:total] == -7))
+        assert bool(torch.all(sent["cells"][total:] == -7)) and bool(torch.all(sent["hop_d"][total:] == -7))
+
+
 def test_lsqr_on_a_golden_box_matches_scipy(P):
     """A short damped lsqr with the operator recovers scipy's lsqr on the dense G.  G is rank-deficient (a cell
     no ray crosses has a zero column), so the damping is a fair fraction of ||G|| (about 240): without it, loss of

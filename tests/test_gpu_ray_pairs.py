@@ -236,6 +236,73 @@ def test_several_boxes_in_one_wave(P, g9_boxes, npair):
         assert np.count_nonzero(got["hops"] == 0) >= 1 and got["hops"].max() >= 1
 
 
+def test_one_context_many_shapes_of_call(P, g9_boxes):
+    """The ray calls share one device buffer of the context, laid out anew by every call, grown when a call needs
+    more and kept between calls.  One solver runs calls of very different sizes in a row - small after large, pair
+    list after cross product, the trace's extra arrays in between - and every result equals, bit for bit, the same
+    call on a fresh solver."""
+    import torch
+    v, fs, starts, boxes, _ = g9_boxes
+    rng = np.random.default_rng(404)
+    box, recv = mixed_pairs(rng, starts, v.shape, 1000)
+    every = all_cells(v.shape)
+    m = torch.from_numpy(rng.uniform(0.5, 2.0, v.size)).to(dev())
+    w_dense = torch.from_numpy(weights(rng, len(starts) * len(every))).to(dev())
+    host = lambda *ts: [t.cpu().numpy().copy() for t in ts]
+
+    def geometry_of_one_pair(sol, tt, pred):
+        geo = sol.ray_geometry(starts, tt, box[:1], recv[:1], pred=pred)
+        return host(geo.status, *[getattr(geo, k) for k in GEO])
+
+    def dense_adjoint_with_hits(sol, tt, pred):
+        op = sol.frechet_operator(starts, tt, every, pred)
+        g, hits = op.rmatvec_hits(w_dense)
+        return host(op.status, g, hits) + [np.array(op.last_scale)]
+
+    def trace_with_one_receiver(sol, tt, pred):
+        rays = sol.trace_rays(starts, tt, recv[7:8], pred)
+        return host(rays.offsets, rays.cells, rays.hop_d, rays.status, rays.t_recv)
+
+    def pair_forward_of_1000_pairs(sol, tt, pred):
+        op = sol.frechet_operator(starts, tt, pred=pred, pairs=(box, recv))
+        return host(op.status, op.matvec(m))
+
+    def predecessors(sol, tt, pred):
+        return host(sol.predecessors(starts, tt))
+
+    def dense_forward_with_one_receiver(sol, tt, pred):
+        op = sol.frechet_operator(starts, tt, recv[3:4], pred)
+        return host(op.status, op.matvec(m))
+
+    def pair_adjoint_of_no_pairs(sol, tt, pred):
+        # (through the C ABI: an empty weight tensor has no pointer to give)
+        n = len(starts)
+        g = torch.full((v.size,), -7.0, dtype=torch.float64, device=dev())
+        hits = torch.full((v.size,), -7, dtype=torch.int32, device=dev())
+        scale = C.c_int(-7)
+        torch.cuda.synchronize()
+        assert P._lib.lib().ttsweep_ray_pairs_adjoint_device(
+            sol._ctx, n, sol._starts_array(starts), sol._box_pointers(tt, n), sol._box_pointers(pred, n), 0, None,
+            None, m.data_ptr(), g.data_ptr(), hits.data_ptr(), C.byref(scale)) == 0, P._lib.last_error()
+        return host(g, hits) + [np.array(scale.value)]
+
+    calls = [geometry_of_one_pair, dense_adjoint_with_hits, trace_with_one_receiver, pair_forward_of_1000_pairs,
+             predecessors, dense_forward_with_one_receiver, pair_adjoint_of_no_pairs]
+    tt = torch.from_numpy(boxes.copy()).to(dev())
+    with solver_for(P, v, fs) as sol:
+        pred = sol.predecessors(starts, tt)
+    want = []
+    for call in calls:
+        with solver_for(P, v, fs) as fresh:
+            want.append(call(fresh, tt, pred))
+    with solver_for(P, v, fs) as sol:
+        got = [call(sol, tt, pred) for call in calls]
+    for call, a, b in zip(calls, got, want):
+        assert len(a) == len(b) and all(same(x, y) for x, y in zip(a, b)), call.__name__
+    assert same(got[4][0], pred.cpu().numpy())
+    assert got[2][0][-1] > len(starts) and len(got[3][1]) == 1000 and not got[6][0].any() and got[6][2] == 0
+
+
 # ---- 3. statuses ----
 def status_pairs(rng, starts, shape, must, npair=300):
     """Random pairs over every box, the cells `must` ([(box, flat cell)]) among them."""

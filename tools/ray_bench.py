@@ -19,7 +19,9 @@ frechet_peak_bytes is the peak of torch's device allocator over (c), the boxes a
 leaves out (b) and (d), the legs that store paths: with --grid 1024,1024,512 --star six --nstarts 14 the paths of
 every surface cell would need ~150 GB.  Prints one JSON line.
 
-    python tools/ray_bench.py [--grid 241,241,51] [--star 818] [--nstarts 24] [--reps 5] [--no-trace]
+    python tools/ray_bench.py [--grid 241,241,51] [--star 818] [--nstarts 24] [--reps 5] [--no-trace] [--lib LIB]
+
+--lib LIB: another build of the library (an A/B build of the same sources); the line's "library" names the one in use.
 """
 import argparse
 import json
@@ -41,10 +43,13 @@ def main():
     ap.add_argument("--nstarts", type=int, default=0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-trace", action="store_true", help="leave out the legs that store paths: (b) and (d)")
+    ap.add_argument("--lib", default=None, help="another build of libttsweep.so (A/B builds)")
     args = ap.parse_args()
     import torch
     import ttsweep_pkg
     P = ttsweep_pkg.load()
+    if args.lib:
+        P._lib.use_library(args.lib)
     nx, ny, nz = (int(x) for x in args.grid.split(","))
     shape = (nx, ny, nz)
     dev = torch.device("cuda:0")
@@ -136,7 +141,8 @@ def main():
         "grid": list(shape), "star": args.star, "nstart": nstart, "solve_kernel_variant": kernel,
         "solve_ms_first_call": round(solve_ms, 3),
         "predecessors_ms": round(pred_ms, 3), "predecessors_ms_all": [round(x, 3) for x in pred_all],
-        "predecessor_candidates": int(nstart * nx * ny * nz * npull), **out}))
+        "predecessor_candidates": int(nstart * nx * ny * nz * npull), **out,
+        "library": os.path.relpath(P._lib.LIB_PATH, ROOT)}))
 
 
 def operator_legs(P, sol, starts, tt, recv, pred, timed, dev):

@@ -14,7 +14,9 @@ return), median of --reps after one warm-up call.
 
 Prints one JSON line.
 
-    python tools/ray_pairs_bench.py [--events 4096] [--reps 5]
+    python tools/ray_pairs_bench.py [--events 4096] [--reps 5] [--lib LIB]
+
+--lib LIB: another build of the library (an A/B build of the same sources); the line's "library" names the one in use.
 """
 import argparse
 import json
@@ -34,11 +36,14 @@ def main():
     ap.add_argument("--events", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--nstarts", type=int, default=0)
+    ap.add_argument("--lib", default=None, help="another build of libttsweep.so (A/B builds)")
     args = ap.parse_args()
     import torch
     import ttsweep_pkg
     from locate_bench import events
     P = ttsweep_pkg.load()
+    if args.lib:
+        P._lib.use_library(args.lib)
     shape = (241, 241, 51)
     nx, ny, nz = shape
     dev = torch.device("cuda:0")

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "pullstar.h"
+#include "scratch_layout.h"
 #include "ttsweep_dev.h"
 #include "ttsweep_kernels.h"
 
@@ -27,33 +28,21 @@ namespace ttsweep {
 // error text of the calling thread (ttsweep_last_error); returns -1
 int set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 
-// The device scratch of one call: add() declares the arrays, alloc() allocates them as one block, each aligned to 256
-// bytes, and sets the pointers in the order of their declaration
-class Scratch {
+// The device scratch of one call: add() declares the arrays (scratch_layout.h), alloc() allocates them as one block
+// of its own, freed with the object.  (The ray calls place the same layout into ctx->d_rays instead.)
+class Scratch : public ScratchLayout {
     char *p = nullptr;
-    size_t bytes = 0;
-    std::vector<std::pair<void *, size_t>> slots;      // where a pointer is kept, and its offset
 
 public:
     ~Scratch()
     {
         if (p) (void)hipFree(p);
     }
-    template <typename T>
-    void add(T *&ptr, size_t n)
-    {
-        slots.push_back({&ptr, bytes});
-        bytes += (n * sizeof(T) + 255) & ~(size_t)255;
-    }
     hipError_t alloc()
     {
-        const hipError_t err = hipMalloc((void **)&p, bytes);
-        if (err != hipSuccess) return err;
-        for (const auto &s : slots) {
-            char *q = p + s.second;
-            memcpy(s.first, &q, sizeof(q));
-        }
-        return hipSuccess;
+        const hipError_t err = hipMalloc((void **)&p, size());
+        if (err == hipSuccess) place(p);
+        return err;
     }
 };
 
@@ -269,5 +258,28 @@ void order_units(const ttsweep_ctx *ctx, const StartDesc &sd, std::vector<int> &
 // The driver loop on device-resident boxes; returns 1 / 0 / < 0 like ttsweep_solve_device.
 int solve_device_body(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
                       float *const *tt_dev, int init);
+
+// ---- ttsweep_rays.cpp: the int64 fixed-point adjoints of the rays and of the Fresnel volumes ----------------
+// The scan of the n doubles at v: *e - 2048 = the largest frexp exponent of a nonzero one (*e = 0: all zero), *bad:
+// one is NaN or infinite (the caller's refusal, in its own words).  d_scan: two ints of device memory.  Drains the
+// stream.
+int fixed_point_scan(ttsweep_ctx *ctx, const double *v, long long n, int *d_scan, int *e, bool *bad);
+
+// The tail of an adjoint whose terms are added in units of 2^-S (the caller's own shift formula): g (the cells of
+// the grid, as int64 while the sums run) and hits zeroed - each may be nullptr -, launch() when there is a weight
+// or hits to add (0, or < 0 with the error set), g to double, the stream drained, *scale = S.
+template <class Launch>
+int fixed_point_adjoint(ttsweep_ctx *ctx, bool weighted, int S, double *g_dev, int *hits_dev, int *scale,
+                        Launch launch)
+{
+    const long long ncells = (long long)ctx->nx * ctx->ny * ctx->nz;
+    if (g_dev) HIPCHK(hipMemsetAsync(g_dev, 0, ncells * sizeof(double), ctx->stream));
+    if (hits_dev) HIPCHK(hipMemsetAsync(hits_dev, 0, ncells * sizeof(int), ctx->stream));
+    if ((weighted || hits_dev) && launch()) return -1;
+    if (weighted) HIPCHK(launch_ray_fixed_to_double((long long *)g_dev, ncells, S, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (scale) *scale = S;
+    return 0;
+}
 
 } // namespace ttsweep

@@ -21,13 +21,6 @@ namespace {
 // (mirrored: tests/test_gpu_fresnel.py::test_a_launch_edge)
 constexpr long long FRES_LAUNCH_BLOCKS = 1LL << 16;
 
-int ceil_log2(long long n)
-{
-    int k = 0;
-    while ((1LL << k) < n) k++;
-    return k;
-}
-
 // tau > 0 and finite, on the bits (the library is built with -fno-honor-nans)
 bool tau_ok(double tau)
 {
@@ -152,19 +145,13 @@ int run_blocks(const Prepared &P, Launch launch)
     return 0;
 }
 
-// out[0] - 2048 = the largest frexp exponent of the n values at v (out[0] = 0: all zero); a NaN or infinite one is
-// refused
+// e - 2048 = the largest frexp exponent of the n values at v (e = 0: all zero); a NaN or infinite one is refused
 int scan_values(const char *what, const char *name, ttsweep_ctx *ctx, const double *v, long long n, int *d_scan,
                 int &e)
 {
-    int scan[2] = {0, 0};
-    HIPCHK(hipMemsetAsync(d_scan, 0, 2 * sizeof(int), ctx->stream));
-    HIPCHK(launch_ray_weight_scan(v, (int)n, d_scan, ctx->stream));
-    HIPCHK(hipMemcpyAsync(scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (scan[1]) return set_error("%s: %s holds a NaN or infinite value", what, name);
-    e = scan[0];
-    return 0;
+    bool bad = false;
+    if (fixed_point_scan(ctx, v, n, d_scan, &e, &bad)) return -1;
+    return bad ? set_error("%s: %s holds a NaN or infinite value", what, name) : 0;
 }
 
 } // namespace
@@ -232,25 +219,20 @@ int ttsweep_fresnel_adjoint_device(ttsweep_ctx *ctx, int nbox, const ttsweep_sta
     if (npair > 0 && !w_dev != !g_dev) return set_error("%s: w and g must both be given or both be NULL", what);
     Prepared P;
     if (prepare(what, ctx, nbox, starts, tt_dev, npair, pair_a, pair_b, tau, lo, hi, true, false, P)) return -1;
-    const long long ncells = (long long)ctx->nx * ctx->ny * ctx->nz;
     // S = 61 - E_w - K: a visit adds less than 2^(E_w + S) = 2^(61 - K) in magnitude (phi <= 1) and a cell is visited
     // by at most 2^K pairs, so |acc[x]| < 2^61
     int e = 0;
     if (w_dev && npair > 0 && scan_values(what, "w", ctx, w_dev, npair, P.d_scan, e)) return -1;
     const int S = e ? 61 - (e - 2048) - ceil_log2(npair) : 0;
-    if (g_dev) HIPCHK(hipMemsetAsync(g_dev, 0, ncells * sizeof(double), ctx->stream));
-    if (hits_dev) HIPCHK(hipMemsetAsync(hits_dev, 0, ncells * sizeof(int), ctx->stream));
-    if (e || hits_dev)
-        if (run_blocks(P, [&](long long b0, int nb) {
-                return launch_fresnel_adjoint(P.d_pairs, P.d_first, P.npair, b0, nb, P.d_tab, ctx->ny * ctx->nz,
-                                              ctx->nz, S, e ? w_dev : nullptr, e ? (long long *)g_dev : nullptr,
-                                              hits_dev, ctx->stream);
-            }))
-            return -1;
-    if (e) HIPCHK(launch_ray_fixed_to_double((long long *)g_dev, ncells, S, ctx->stream));
-    if (finish(ctx, P, status)) return -1;
-    if (scale) *scale = S;
-    return 0;
+    const auto blocks = [&] {
+        return run_blocks(P, [&](long long b0, int nb) {
+            return launch_fresnel_adjoint(P.d_pairs, P.d_first, P.npair, b0, nb, P.d_tab, ctx->ny * ctx->nz, ctx->nz,
+                                          S, e ? w_dev : nullptr, e ? (long long *)g_dev : nullptr, hits_dev,
+                                          ctx->stream);
+        });
+    };
+    if (finish(ctx, P, status)) return -1;          // (the statuses are prepare()'s)
+    return fixed_point_adjoint(ctx, e != 0, S, g_dev, hits_dev, scale, blocks);
 }
 
 } // extern "C"

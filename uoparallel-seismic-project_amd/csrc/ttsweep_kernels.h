@@ -158,32 +158,25 @@ struct RayGeom {
     int pad_;
     long long vbase, vs[3];
 };
-// pred[s][c] for every cell of every box (TTSWEEP_PRED_* or the smallest flat index of a predecessor)
-hipError_t launch_predecessors(const RayGeom &G, const float *v, const RayBox *boxes, int nstart,
-                               const RayEntry *entries, int nentries, bool exact, hipStream_t st);
-// fill = false: count[r], status[r], t_recv[r] of every ray r = s * nrecv + q; fill = true: also the cells and
-// hop lengths of the OK / SEED rays at [offsets[r], offsets[r + 1]) of cells / hop_d (written backwards, so a
-// path reads source -> receiver; hop_d[offsets[r + 1] - 1] = 0)
-hipError_t launch_trace_rays(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
-                             int nrecv, const RayEntry *entries, int nentries, bool exact, int *count, int *status,
-                             float *t_recv, const long long *offsets, int *cells, float *hop_d, bool fill,
-                             hipStream_t st);
-
-// the Frechet operators of the rays (status[r] of every ray; acc: the caller's g read as int64, zeroed first)
-hipError_t launch_ray_forward(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
-                              int nrecv, const RayEntry *entries, int nentries, bool exact, const double *m,
-                              double *y, int *status, hipStream_t st);
-// out[0] = max (frexp exponent + 2048) of the nonzero w (0: none), out[1] = 1 if a w is NaN or infinite; zeroed first
-hipError_t launch_ray_weight_scan(const double *w, int n, int *out, hipStream_t st);
-hipError_t launch_ray_adjoint(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
-                              int nrecv, const RayEntry *entries, int nentries, bool exact, const double *w, int S,
-                              long long *acc, int *hits, hipStream_t st);
-// g[x] = ldexp((double)acc[x], -S) in place
-hipError_t launch_ray_fixed_to_double(long long *g, long long n, int S, hipStream_t st);
-
 // pair lists: ray r is the ray of box pairs[r].box from the cell of FLOATBOX index pairs[r].recv
 struct alignas(8) RayPair {
     int box, recv;
+};
+// what every ray kernel reads, passed by value: the grid, the padded velocity, the box records and the star's entries
+struct RayArgs {
+    RayGeom G;
+    const float *v;
+    const RayBox *boxes;
+    const RayEntry *entries;
+    int nentries;
+};
+// the n rays of a call: the cross product r = s * nrecv + q of the boxes with the receivers recv[q] (FLOATBOX
+// indices; pairs == nullptr), or the records of a pair list (recv == nullptr)
+struct RayList {
+    const int *recv;
+    int nrecv;
+    const RayPair *pairs;
+    long long n;
 };
 // the outputs of the geometry kernel, each [npair] (recv_hop, src_hop: [npair][3]) on the device or nullptr
 struct RayGeometryOut {
@@ -196,16 +189,25 @@ struct RayGeometryOut {
     float *src_d, *src_dt;
     int *deep;
 };
-// the operators and the geometry over a pair list (status[r] of every pair; acc as in launch_ray_adjoint)
-hipError_t launch_ray_pairs_forward(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
-                                    int npair, const RayEntry *entries, int nentries, bool exact, const double *m,
-                                    double *y, int *status, hipStream_t st);
-hipError_t launch_ray_pairs_adjoint(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
-                                    int npair, const RayEntry *entries, int nentries, bool exact, const double *w,
-                                    int S, long long *acc, int *hits, hipStream_t st);
-hipError_t launch_ray_pairs_geometry(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
-                                     int npair, const RayEntry *entries, int nentries, bool exact, int *status,
+// pred[s][c] for every cell of every box (TTSWEEP_PRED_* or the smallest flat index of a predecessor)
+hipError_t launch_predecessors(const RayArgs &A, int nstart, bool exact, hipStream_t st);
+// fill = false: count[r], status[r], t_recv[r] of every ray r of a cross product (of any size: 64-bit ray indices);
+// fill = true: also the cells and hop lengths of the OK / SEED rays at [offsets[r], offsets[r + 1]) of cells / hop_d
+// (written backwards, so a path reads source -> receiver; hop_d[offsets[r + 1] - 1] = 0)
+hipError_t launch_trace_rays(const RayArgs &A, const RayList &L, bool exact, int *count, int *status, float *t_recv,
+                             const long long *offsets, int *cells, float *hop_d, bool fill, hipStream_t st);
+// the Frechet operators of the rays of either kind of list, at most INT32_MAX of them (status[r] of every ray; acc:
+// the caller's g read as int64, zeroed first), and the geometry of the rays of a pair list
+hipError_t launch_ray_forward(const RayArgs &A, const RayList &L, bool exact, const double *m, double *y, int *status,
+                              hipStream_t st);
+hipError_t launch_ray_adjoint(const RayArgs &A, const RayList &L, bool exact, const double *w, int S, long long *acc,
+                              int *hits, hipStream_t st);
+hipError_t launch_ray_pairs_geometry(const RayArgs &A, const RayList &L, bool exact, int *status,
                                      const RayGeometryOut &out, hipStream_t st);
+// out[0] = max (frexp exponent + 2048) of the nonzero w (0: none), out[1] = 1 if a w is NaN or infinite; zeroed first
+hipError_t launch_ray_weight_scan(const double *w, int n, int *out, hipStream_t st);
+// g[x] = ldexp((double)acc[x], -S) in place
+hipError_t launch_ray_fixed_to_double(long long *g, long long n, int S, hipStream_t st);
 
 // event location (ttsweep_locate.hip; every search there is one scan, loc_scan, over its own kind of candidate, and
 // the three argmin searches share the per-lane minima and the final).  check: invw[e] = 1.0 / W and flag[e] (bit 0 a

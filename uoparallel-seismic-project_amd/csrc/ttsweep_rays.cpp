@@ -1,7 +1,8 @@
 // ttsweep_rays.cpp - the ray calls of include/ttsweep.h: ttsweep_predecessors_device,
 // ttsweep_trace_rays_device, the Frechet operators ttsweep_ray_forward_device / ttsweep_ray_adjoint_device and
 // their pair-list forms ttsweep_ray_pairs_{forward,adjoint,geometry}_device (kernels: ttsweep_rays.hip).
-// Argument checks, the star's ray entries, the host-side scan of the per-ray cell counts.  Nothing here touches the solve's state: the boxes the
+// Argument checks, the star's ray entries, one staging of the device arrays for all seven calls, the host-side scan of
+// the per-ray cell counts, the fixed-point helpers the Fresnel calls share.  Nothing here touches the solve's state: the boxes the
 // confirming-pass shortcut of ttsweep_solve remembers, its pools and its options stay as they are.
 #include "ttsweep_ctx.h"
 
@@ -15,8 +16,6 @@ using namespace ttsweep;
 
 namespace {
 
-size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
 bool inside(const ttsweep_ctx *ctx, const ttsweep_start &p)
 {
     return p.i >= 0 && p.i < ctx->nx && p.j >= 0 && p.j < ctx->ny && p.k >= 0 && p.k < ctx->nz;
@@ -26,7 +25,7 @@ int flat(const ttsweep_ctx *ctx, const ttsweep_start &p) { return (p.i * ctx->ny
 
 // what both calls check before any device work
 int check_boxes(const ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float *const *tt_dev,
-                const void *const *pred_dev, const char *what)
+                const int *const *pred_dev, const char *what)
 {
     if (!ctx || nstart < 0 || (nstart > 0 && (!starts || !tt_dev || !pred_dev)))
         return set_error("%s: null or bad argument", what);
@@ -41,6 +40,19 @@ int check_boxes(const ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
     }
     return 0;
 }
+
+// the boxes and the rays of a call once its checks have passed: the cross product of the boxes with recv (FLOATBOX
+// indices), or the records of a pair list
+struct RayInput {
+    int nstart = 0;
+    const ttsweep_start *starts = nullptr;
+    const float *const *tt_dev = nullptr;
+    const int *const *pred_dev = nullptr;
+    bool by_pairs = false;
+    std::vector<int> recv;
+    std::vector<RayPair> pairs;
+    long long nrays() const { return by_pairs ? (long long)pairs.size() : (long long)nstart * (long long)recv.size(); }
+};
 
 // the receivers as FLOATBOX indices; each must lie inside the grid
 int flat_receivers(const ttsweep_ctx *ctx, int nrecv, const ttsweep_start *receivers, const char *what,
@@ -60,13 +72,37 @@ int flat_receivers(const ttsweep_ctx *ctx, int nrecv, const ttsweep_start *recei
 // boxes, the receivers
 int check_operator(const ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float *const *tt_dev,
                    const int *const *pred_dev, int nrecv, const ttsweep_start *receivers, const char *what,
-                   std::vector<int> &recv)
+                   RayInput &in)
 {
     if (nstart < 0 || nrecv < 0 || (nrecv > 0 && !receivers)) return set_error("%s: null or bad argument", what);
     if ((long long)nstart * nrecv > INT_MAX)
         return set_error("%s: %d starts x %d receivers do not fit int32 ray indices", what, nstart, nrecv);
-    if (check_boxes(ctx, nstart, starts, tt_dev, (const void *const *)pred_dev, what)) return -1;
-    return flat_receivers(ctx, nrecv, receivers, what, recv);
+    if (check_boxes(ctx, nstart, starts, tt_dev, pred_dev, what)) return -1;
+    in = RayInput{nstart, starts, tt_dev, pred_dev};
+    return flat_receivers(ctx, nrecv, receivers, what, in.recv);
+}
+
+// the checks of the three pair-list calls before any device work: the pair count (one int32 index per ray), the
+// boxes, every pair; the pairs as device records
+int check_pairs(const ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float *const *tt_dev,
+                const int *const *pred_dev, long long npair, const int *pair_box, const ttsweep_start *pair_recv,
+                const char *what, RayInput &in)
+{
+    if (nstart < 0 || npair < 0) return set_error("%s: null or bad argument", what);
+    if (npair > INT_MAX) return set_error("%s: %lld pairs do not fit int32 ray indices", what, npair);
+    if (npair > 0 && (!pair_box || !pair_recv)) return set_error("%s: null or bad argument", what);
+    if (check_boxes(ctx, nstart, starts, tt_dev, pred_dev, what)) return -1;
+    in = RayInput{nstart, starts, tt_dev, pred_dev, true};
+    in.pairs.resize(npair);
+    for (long long r = 0; r < npair; r++) {
+        if (pair_box[r] < 0 || pair_box[r] >= nstart)
+            return set_error("%s: pair %lld names box %d, not in [0, %d)", what, r, pair_box[r], nstart);
+        if (!inside(ctx, pair_recv[r]))
+            return set_error("%s: receiver of pair %lld (%d, %d, %d) outside the grid", what, r, pair_recv[r].i,
+                             pair_recv[r].j, pair_recv[r].k);
+        in.pairs[r] = RayPair{pair_box[r], flat(ctx, pair_recv[r])};
+    }
+    return 0;
 }
 
 // the grid in the caller's axes over the padded velocity volume of the current layout
@@ -119,116 +155,140 @@ int ensure_ray_buffer(ttsweep_ctx *ctx, size_t bytes)
     return 0;
 }
 
-// entries and box records on the device, at the front of ctx->d_rays (extra: bytes the caller needs behind them)
-struct RayStage {
-    RayGeom G;
+// What a ray call holds once stage() has run: the arguments of its kernels (A, L: the entries, the box records and
+// the receivers or pair records, uploaded) and the per-ray arrays it copies back, all of them in ctx->d_rays
+struct Staged {
     std::vector<RayEntry> ent;
     std::vector<RayBox> boxes;
-    RayEntry *d_ent = nullptr;
-    RayBox *d_boxes = nullptr;
-    char *rest = nullptr;
+    RayArgs A{};
+    RayList L{};
+    int *d_status = nullptr, *d_scan = nullptr;
+    int *d_count = nullptr;             // trace only: cells per ray, t_recv and the offsets of the fill pass
+    float *d_trecv = nullptr;
+    long long *d_offsets = nullptr;
 };
 
-int stage(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float *const *tt_dev,
-          int *const *pred_dev, size_t extra, RayStage &S)
+// The preparation every ray call shares once it is not refused: the device, the layout of its arrays in ctx->d_rays
+// (grown when it does not hold them), the upload of the entries, the boxes and the list of rays.  The host arrays
+// behind the copies (S, in) live until the caller has synchronised.
+int stage(ttsweep_ctx *ctx, const RayInput &in, bool trace, Staged &S)
 {
-    S.G = ray_geom(ctx);
-    S.ent = ray_entries(ctx, S.G);
-    S.boxes.resize(nstart);
-    for (int s = 0; s < nstart; s++) S.boxes[s] = RayBox{tt_dev[s], pred_dev[s], flat(ctx, starts[s]), 0};
-    const size_t be = align_up(std::max<size_t>(S.ent.size(), 1) * sizeof(RayEntry));
-    const size_t bb = align_up(std::max(nstart, 1) * sizeof(RayBox));
-    if (ensure_ray_buffer(ctx, be + bb + extra)) return -1;
-    S.d_ent = (RayEntry *)ctx->d_rays;
-    S.d_boxes = (RayBox *)(ctx->d_rays + be);
-    S.rest = ctx->d_rays + be + bb;
-    if (!S.ent.empty())
-        HIPCHK(hipMemcpyAsync(S.d_ent, S.ent.data(), S.ent.size() * sizeof(RayEntry), hipMemcpyHostToDevice,
-                              ctx->stream));
-    if (nstart)
-        HIPCHK(hipMemcpyAsync(S.d_boxes, S.boxes.data(), nstart * sizeof(RayBox), hipMemcpyHostToDevice,
-                              ctx->stream));
-    return 0;
-}
-
-// the checks of the three pair-list calls before any device work: the pair count (one int32 index per ray), the
-// boxes, every pair; the pairs as device records
-int check_pairs(const ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts, const float *const *tt_dev,
-                const int *const *pred_dev, long long npair, const int *pair_box, const ttsweep_start *pair_recv,
-                const char *what, std::vector<RayPair> &pairs)
-{
-    if (nstart < 0 || npair < 0) return set_error("%s: null or bad argument", what);
-    if (npair > INT_MAX) return set_error("%s: %lld pairs do not fit int32 ray indices", what, npair);
-    if (npair > 0 && (!pair_box || !pair_recv)) return set_error("%s: null or bad argument", what);
-    if (check_boxes(ctx, nstart, starts, tt_dev, (const void *const *)pred_dev, what)) return -1;
-    pairs.resize(npair);
-    for (long long r = 0; r < npair; r++) {
-        if (pair_box[r] < 0 || pair_box[r] >= nstart)
-            return set_error("%s: pair %lld names box %d, not in [0, %d)", what, r, pair_box[r], nstart);
-        if (!inside(ctx, pair_recv[r]))
-            return set_error("%s: receiver of pair %lld (%d, %d, %d) outside the grid", what, r, pair_recv[r].i,
-                             pair_recv[r].j, pair_recv[r].k);
-        pairs[r] = RayPair{pair_box[r], flat(ctx, pair_recv[r])};
+    if (ctx_bind(ctx)) return -1;
+    S.A.G = ray_geom(ctx);
+    S.A.v = ctx->d_v;
+    S.ent = ray_entries(ctx, S.A.G);
+    S.A.nentries = (int)S.ent.size();
+    S.boxes.resize(in.nstart);
+    for (int s = 0; s < in.nstart; s++)
+        S.boxes[s] = RayBox{in.tt_dev[s], (int *)in.pred_dev[s], flat(ctx, in.starts[s]), 0};
+    S.L.nrecv = (int)in.recv.size();
+    S.L.n = in.nrays();
+    ScratchLayout lay;
+    lay.add(S.A.entries, S.ent.size());
+    lay.add(S.A.boxes, S.boxes.size());
+    if (in.by_pairs) lay.add(S.L.pairs, in.pairs.size());
+    else lay.add(S.L.recv, in.recv.size());
+    lay.add(S.d_status, S.L.n);
+    if (trace) {
+        lay.add(S.d_count, S.L.n);
+        lay.add(S.d_trecv, S.L.n);
+        lay.add(S.d_offsets, S.L.n + 1);
     }
+    lay.add(S.d_scan, 2);
+    if (ensure_ray_buffer(ctx, lay.size())) return -1;
+    lay.place(ctx->d_rays);
+    auto upload = [&](const void *dst, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(const_cast<void *>(dst), src, bytes, hipMemcpyHostToDevice, ctx->stream)
+                     : hipSuccess;
+    };
+    HIPCHK(upload(S.A.entries, S.ent.data(), S.ent.size() * sizeof(RayEntry)));
+    HIPCHK(upload(S.A.boxes, S.boxes.data(), S.boxes.size() * sizeof(RayBox)));
+    HIPCHK(upload(S.L.recv, in.recv.data(), in.recv.size() * sizeof(int)));
+    HIPCHK(upload(S.L.pairs, in.pairs.data(), in.pairs.size() * sizeof(RayPair)));
     return 0;
 }
 
-// The adjoint of nrays rays once the boxes and the rays' records are staged: the weights' scan (a NaN or infinite
-// weight is refused before g is touched), S = 61 - E_w - E_d - K, the zeroed accumulators, launch(w, S) and the
-// conversion of g.  d_scan: two ints of the ray buffer.
-template <class Launch>
-int run_adjoint(ttsweep_ctx *ctx, const char *what, const RayStage &S, long long nrays, int *d_scan,
-                const double *w_dev, double *g_dev, int *hits_dev, int *scale, Launch launch)
+// the end of a call that was not refused: the statuses to the host, and the stream drained
+int finish(ttsweep_ctx *ctx, const Staged &S, int *status)
 {
-    const long long ncells = (long long)ctx->nx * ctx->ny * ctx->nz;
+    if (status && S.L.n)
+        HIPCHK(hipMemcpyAsync(status, S.d_status, S.L.n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// G m of the rays of either kind of list, after the list's own checks
+int run_forward(ttsweep_ctx *ctx, const char *what, const RayInput &in, const double *m_dev, double *y_dev,
+                int *status)
+{
+    if (in.nrays() == 0) return 0;
+    if (!m_dev || !y_dev) return set_error("%s: null or bad argument", what);
+    Staged S;
+    if (stage(ctx, in, false, S)) return -1;
+    HIPCHK(launch_ray_forward(S.A, S.L, ctx->exact_half, m_dev, y_dev, S.d_status, ctx->stream));
+    return finish(ctx, S, status);
+}
+
+// G^T w and the hits of the rays of either kind of list, after the list's own checks: the weights' scan (a NaN or
+// infinite weight is refused before g is touched), the shift, the zeroed accumulators, the walk and the conversion
+// of g
+int run_adjoint(ttsweep_ctx *ctx, const char *what, const RayInput &in, const double *w_dev, double *g_dev,
+                int *hits_dev, int *scale)
+{
+    if (!w_dev != !g_dev) return set_error("%s: w and g must both be given or both be NULL", what);
+    if (!g_dev && !hits_dev) {
+        if (scale) *scale = 0;
+        return 0;
+    }
+    Staged S;
+    if (stage(ctx, in, false, S)) return -1;
     // S = 61 - E_w - E_d - K: a visit adds less than 2^(E_w + E_d + S) = 2^(61 - K) in magnitude, a ray visits a
     // cell at most once (T strictly decreases along it) and there are at most 2^K rays, so |acc[x]| < 2^61
-    int shift = 0;
-    bool weighted = false;
-    if (w_dev && nrays > 0) {
-        int scan[2] = {0, 0};
-        HIPCHK(hipMemsetAsync(d_scan, 0, 2 * sizeof(int), ctx->stream));
-        HIPCHK(launch_ray_weight_scan(w_dev, (int)nrays, d_scan, ctx->stream));
-        HIPCHK(hipMemcpyAsync(scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (scan[1]) return set_error("%s: a weight is NaN or infinite", what);
-        if (scan[0]) {
-            float dmax = 0.0f;
-            for (const RayEntry &e : S.ent) dmax = std::max(dmax, e.d);
-            int e_d = 0;
-            std::frexp((double)dmax, &e_d);
-            int k = 0;
-            while ((1LL << k) < nrays) k++;
-            shift = 61 - (scan[0] - 2048) - e_d - k;
-            weighted = true;
-        }
+    const long long nrays = in.nrays();
+    int e_w = 0, shift = 0;
+    bool bad = false;
+    if (w_dev && nrays > 0 && fixed_point_scan(ctx, w_dev, nrays, S.d_scan, &e_w, &bad)) return -1;
+    if (bad) return set_error("%s: a weight is NaN or infinite", what);
+    if (e_w) {
+        float dmax = 0.0f;
+        for (const RayEntry &e : S.ent) dmax = std::max(dmax, e.d);
+        int e_d = 0;
+        std::frexp((double)dmax, &e_d);
+        shift = 61 - (e_w - 2048) - e_d - ceil_log2(nrays);
     }
-    if (g_dev) HIPCHK(hipMemsetAsync(g_dev, 0, ncells * sizeof(double), ctx->stream));
-    if (hits_dev) HIPCHK(hipMemsetAsync(hits_dev, 0, ncells * sizeof(int), ctx->stream));
-    if (weighted || hits_dev) HIPCHK(launch(weighted ? w_dev : nullptr, shift));
-    if (weighted) HIPCHK(launch_ray_fixed_to_double((long long *)g_dev, ncells, shift, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (scale) *scale = shift;
-    return 0;
+    return fixed_point_adjoint(ctx, e_w != 0, shift, g_dev, hits_dev, scale, [&] {
+        HIPCHK(launch_ray_adjoint(S.A, S.L, ctx->exact_half, e_w ? w_dev : nullptr, shift, (long long *)g_dev,
+                                  hits_dev, ctx->stream));
+        return 0;
+    });
 }
 
 } // namespace
+
+int ttsweep::fixed_point_scan(ttsweep_ctx *ctx, const double *v, long long n, int *d_scan, int *e, bool *bad)
+{
+    int scan[2] = {0, 0};
+    HIPCHK(hipMemsetAsync(d_scan, 0, 2 * sizeof(int), ctx->stream));
+    HIPCHK(launch_ray_weight_scan(v, (int)n, d_scan, ctx->stream));
+    HIPCHK(hipMemcpyAsync(scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *e = scan[0];
+    *bad = scan[1] != 0;
+    return 0;
+}
 
 extern "C" {
 
 int ttsweep_predecessors_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
                                 const float *const *tt_dev, int *const *pred_dev)
 {
-    if (check_boxes(ctx, nstart, starts, tt_dev, (const void *const *)pred_dev, "ttsweep_predecessors_device"))
+    if (check_boxes(ctx, nstart, starts, tt_dev, pred_dev, "ttsweep_predecessors_device"))
         return -1;
     if (nstart == 0) return 0;
-    if (ctx_bind(ctx)) return -1;
-    RayStage S;
-    if (stage(ctx, nstart, starts, tt_dev, pred_dev, 0, S)) return -1;
-    HIPCHK(launch_predecessors(S.G, ctx->d_v, S.d_boxes, nstart, S.d_ent, (int)S.ent.size(), ctx->exact_half,
-                               ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));      // (also keeps S's host vectors alive past the copies)
-    return 0;
+    Staged S;
+    if (stage(ctx, RayInput{nstart, starts, tt_dev, pred_dev}, false, S)) return -1;
+    HIPCHK(launch_predecessors(S.A, nstart, ctx->exact_half, ctx->stream));
+    return finish(ctx, S, nullptr);
 }
 
 long long ttsweep_trace_rays_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
@@ -238,42 +298,31 @@ long long ttsweep_trace_rays_device(ttsweep_ctx *ctx, int nstart, const ttsweep_
                                     int *cells_dev, float *hop_d_dev, long long capacity)
 {
     const char *what = "ttsweep_trace_rays_device";
-    if (check_boxes(ctx, nstart, starts, tt_dev, (const void *const *)pred_dev, what)) return -1;
+    if (check_boxes(ctx, nstart, starts, tt_dev, pred_dev, what)) return -1;
     if (nrecv < 0 || (nrecv > 0 && !receivers) || !offsets) return set_error("%s: null or bad argument", what);
-    std::vector<int> recv;
-    if (flat_receivers(ctx, nrecv, receivers, what, recv)) return -1;
-    const long long nrays = (long long)nstart * nrecv;
+    RayInput in{nstart, starts, tt_dev, pred_dev};
+    if (flat_receivers(ctx, nrecv, receivers, what, in.recv)) return -1;
+    const long long nrays = in.nrays();
     offsets[0] = 0;
     if (nrays == 0) return 0;
-    if (ctx_bind(ctx)) return -1;
-    const size_t br = align_up(nrecv * sizeof(int)), bn = align_up(nrays * sizeof(int));
-    const size_t bo = align_up((nrays + 1) * sizeof(long long));
-    RayStage S;
-    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, br + 3 * bn + bo, S)) return -1;
-    int *d_recv = (int *)S.rest;
-    int *d_count = (int *)(S.rest + br);
-    int *d_status = (int *)(S.rest + br + bn);
-    float *d_trecv = (float *)(S.rest + br + 2 * bn);
-    long long *d_offsets = (long long *)(S.rest + br + 3 * bn);
-    HIPCHK(hipMemcpyAsync(d_recv, recv.data(), nrecv * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    const int nent = (int)S.ent.size();
-    HIPCHK(launch_trace_rays(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, nent, ctx->exact_half,
-                             d_count, d_status, d_trecv, nullptr, nullptr, nullptr, false, ctx->stream));
+    Staged S;
+    if (stage(ctx, in, true, S)) return -1;
+    HIPCHK(launch_trace_rays(S.A, S.L, ctx->exact_half, S.d_count, S.d_status, S.d_trecv, nullptr, nullptr, nullptr,
+                             false, ctx->stream));
     std::vector<int> count(nrays);
-    HIPCHK(hipMemcpyAsync(count.data(), d_count, nrays * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d_status, nrays * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (t_recv) HIPCHK(hipMemcpyAsync(t_recv, d_trecv, nrays * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpyAsync(count.data(), S.d_count, nrays * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (t_recv) HIPCHK(hipMemcpyAsync(t_recv, S.d_trecv, nrays * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (finish(ctx, S, status)) return -1;
     long long total = 0;
     for (long long r = 0; r < nrays; r++) {
         total += count[r];
         offsets[r + 1] = total;
     }
     if (cells_dev && hop_d_dev && capacity >= total && total > 0) {
-        HIPCHK(hipMemcpyAsync(d_offsets, offsets, (nrays + 1) * sizeof(long long), hipMemcpyHostToDevice,
+        HIPCHK(hipMemcpyAsync(S.d_offsets, offsets, (nrays + 1) * sizeof(long long), hipMemcpyHostToDevice,
                               ctx->stream));
-        HIPCHK(launch_trace_rays(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, nent, ctx->exact_half,
-                                 d_count, d_status, d_trecv, d_offsets, cells_dev, hop_d_dev, true, ctx->stream));
+        HIPCHK(launch_trace_rays(S.A, S.L, ctx->exact_half, S.d_count, S.d_status, S.d_trecv, S.d_offsets, cells_dev,
+                                 hop_d_dev, true, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     return total;
@@ -285,23 +334,9 @@ int ttsweep_ray_forward_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start
                                const double *m_dev, double *y_dev, int *status)
 {
     const char *what = "ttsweep_ray_forward_device";
-    std::vector<int> recv;
-    if (check_operator(ctx, nstart, starts, tt_dev, pred_dev, nrecv, receivers, what, recv)) return -1;
-    const long long nrays = (long long)nstart * nrecv;
-    if (nrays == 0) return 0;
-    if (!m_dev || !y_dev) return set_error("%s: null or bad argument", what);
-    if (ctx_bind(ctx)) return -1;
-    const size_t br = align_up(nrecv * sizeof(int)), bn = align_up(nrays * sizeof(int));
-    RayStage S;
-    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, br + bn, S)) return -1;
-    int *d_recv = (int *)S.rest;
-    int *d_status = (int *)(S.rest + br);
-    HIPCHK(hipMemcpyAsync(d_recv, recv.data(), nrecv * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(launch_ray_forward(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, (int)S.ent.size(),
-                              ctx->exact_half, m_dev, y_dev, d_status, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d_status, nrays * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return 0;
+    RayInput in;
+    if (check_operator(ctx, nstart, starts, tt_dev, pred_dev, nrecv, receivers, what, in)) return -1;
+    return run_forward(ctx, what, in, m_dev, y_dev, status);
 }
 
 int ttsweep_ray_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
@@ -310,26 +345,9 @@ int ttsweep_ray_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start
                                const double *w_dev, double *g_dev, int *hits_dev, int *scale)
 {
     const char *what = "ttsweep_ray_adjoint_device";
-    std::vector<int> recv;
-    if (check_operator(ctx, nstart, starts, tt_dev, pred_dev, nrecv, receivers, what, recv)) return -1;
-    if (!w_dev != !g_dev) return set_error("%s: w and g must both be given or both be NULL", what);
-    const long long nrays = (long long)nstart * nrecv;
-    if (!g_dev && !hits_dev) {
-        if (scale) *scale = 0;
-        return 0;
-    }
-    if (ctx_bind(ctx)) return -1;
-    const size_t br = align_up(std::max(nrecv, 1) * sizeof(int));
-    RayStage S;
-    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, br + 256, S)) return -1;
-    int *d_recv = (int *)S.rest;
-    int *d_scan = (int *)(S.rest + br);
-    if (nrecv)
-        HIPCHK(hipMemcpyAsync(d_recv, recv.data(), nrecv * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    return run_adjoint(ctx, what, S, nrays, d_scan, w_dev, g_dev, hits_dev, scale, [&](const double *w, int shift) {
-        return launch_ray_adjoint(S.G, ctx->d_v, S.d_boxes, nstart, d_recv, nrecv, S.d_ent, (int)S.ent.size(),
-                                  ctx->exact_half, w, shift, (long long *)g_dev, hits_dev, ctx->stream);
-    });
+    RayInput in;
+    if (check_operator(ctx, nstart, starts, tt_dev, pred_dev, nrecv, receivers, what, in)) return -1;
+    return run_adjoint(ctx, what, in, w_dev, g_dev, hits_dev, scale);
 }
 
 int ttsweep_ray_pairs_forward_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
@@ -338,22 +356,9 @@ int ttsweep_ray_pairs_forward_device(ttsweep_ctx *ctx, int nstart, const ttsweep
                                      const double *m_dev, double *y_dev, int *status)
 {
     const char *what = "ttsweep_ray_pairs_forward_device";
-    std::vector<RayPair> pairs;
-    if (check_pairs(ctx, nstart, starts, tt_dev, pred_dev, npair, pair_box, pair_recv, what, pairs)) return -1;
-    if (npair == 0) return 0;
-    if (!m_dev || !y_dev) return set_error("%s: null or bad argument", what);
-    if (ctx_bind(ctx)) return -1;
-    const size_t bp = align_up(npair * sizeof(RayPair)), bn = align_up(npair * sizeof(int));
-    RayStage S;
-    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, bp + bn, S)) return -1;
-    RayPair *d_pairs = (RayPair *)S.rest;
-    int *d_status = (int *)(S.rest + bp);
-    HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), npair * sizeof(RayPair), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(launch_ray_pairs_forward(S.G, ctx->d_v, S.d_boxes, d_pairs, (int)npair, S.d_ent, (int)S.ent.size(),
-                                    ctx->exact_half, m_dev, y_dev, d_status, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d_status, npair * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return 0;
+    RayInput in;
+    if (check_pairs(ctx, nstart, starts, tt_dev, pred_dev, npair, pair_box, pair_recv, what, in)) return -1;
+    return run_forward(ctx, what, in, m_dev, y_dev, status);
 }
 
 int ttsweep_ray_pairs_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
@@ -362,25 +367,9 @@ int ttsweep_ray_pairs_adjoint_device(ttsweep_ctx *ctx, int nstart, const ttsweep
                                      const double *w_dev, double *g_dev, int *hits_dev, int *scale)
 {
     const char *what = "ttsweep_ray_pairs_adjoint_device";
-    std::vector<RayPair> pairs;
-    if (check_pairs(ctx, nstart, starts, tt_dev, pred_dev, npair, pair_box, pair_recv, what, pairs)) return -1;
-    if (!w_dev != !g_dev) return set_error("%s: w and g must both be given or both be NULL", what);
-    if (!g_dev && !hits_dev) {
-        if (scale) *scale = 0;
-        return 0;
-    }
-    if (ctx_bind(ctx)) return -1;
-    const size_t bp = align_up(std::max<long long>(npair, 1) * sizeof(RayPair));
-    RayStage S;
-    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, bp + 256, S)) return -1;
-    RayPair *d_pairs = (RayPair *)S.rest;
-    int *d_scan = (int *)(S.rest + bp);
-    if (npair)
-        HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), npair * sizeof(RayPair), hipMemcpyHostToDevice, ctx->stream));
-    return run_adjoint(ctx, what, S, npair, d_scan, w_dev, g_dev, hits_dev, scale, [&](const double *w, int shift) {
-        return launch_ray_pairs_adjoint(S.G, ctx->d_v, S.d_boxes, d_pairs, (int)npair, S.d_ent, (int)S.ent.size(),
-                                        ctx->exact_half, w, shift, (long long *)g_dev, hits_dev, ctx->stream);
-    });
+    RayInput in;
+    if (check_pairs(ctx, nstart, starts, tt_dev, pred_dev, npair, pair_box, pair_recv, what, in)) return -1;
+    return run_adjoint(ctx, what, in, w_dev, g_dev, hits_dev, scale);
 }
 
 int ttsweep_ray_pairs_geometry_device(ttsweep_ctx *ctx, int nstart, const ttsweep_start *starts,
@@ -391,23 +380,15 @@ int ttsweep_ray_pairs_geometry_device(ttsweep_ctx *ctx, int nstart, const ttswee
                                       int *src_hop_dev, float *src_d_dev, float *src_dt_dev, int *deep_dev)
 {
     const char *what = "ttsweep_ray_pairs_geometry_device";
-    std::vector<RayPair> pairs;
-    if (check_pairs(ctx, nstart, starts, tt_dev, pred_dev, npair, pair_box, pair_recv, what, pairs)) return -1;
+    RayInput in;
+    if (check_pairs(ctx, nstart, starts, tt_dev, pred_dev, npair, pair_box, pair_recv, what, in)) return -1;
     if (npair == 0) return 0;
-    if (ctx_bind(ctx)) return -1;
-    const size_t bp = align_up(npair * sizeof(RayPair)), bn = align_up(npair * sizeof(int));
-    RayStage S;
-    if (stage(ctx, nstart, starts, tt_dev, (int *const *)pred_dev, bp + bn, S)) return -1;
-    RayPair *d_pairs = (RayPair *)S.rest;
-    int *d_status = (int *)(S.rest + bp);
-    HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), npair * sizeof(RayPair), hipMemcpyHostToDevice, ctx->stream));
+    Staged S;
+    if (stage(ctx, in, false, S)) return -1;
     const RayGeometryOut out{t_recv_dev, hops_dev, length_dev, recv_hop_dev, recv_d_dev, recv_dt_dev,
                              src_hop_dev, src_d_dev, src_dt_dev, deep_dev};
-    HIPCHK(launch_ray_pairs_geometry(S.G, ctx->d_v, S.d_boxes, d_pairs, (int)npair, S.d_ent, (int)S.ent.size(),
-                                     ctx->exact_half, d_status, out, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d_status, npair * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HIPCHK(launch_ray_pairs_geometry(S.A, S.L, ctx->exact_half, S.d_status, out, ctx->stream));
+    return finish(ctx, S, status);
 }
 
 } // extern "C"

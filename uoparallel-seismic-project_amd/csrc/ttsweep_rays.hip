@@ -93,17 +93,15 @@ predecessor_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restr
 }
 
 template <int SB>
-static void launch_pred_sb(dim3 grid, const RayGeom &G, const float *v, const RayBox *boxes, int nstart,
-                           const RayEntry *entries, int nentries, bool exact, hipStream_t st)
+static void launch_pred_sb(dim3 grid, const RayArgs &A, int nstart, bool exact, hipStream_t st)
 {
     auto kernel = exact ? predecessor_kernel<true, SB> : predecessor_kernel<false, SB>;
-    hipLaunchKernelGGL(kernel, grid, dim3(RAY_BLOCK), 0, st, G, v, boxes, nstart, entries, nentries);
+    hipLaunchKernelGGL(kernel, grid, dim3(RAY_BLOCK), 0, st, A.G, A.v, A.boxes, nstart, A.entries, A.nentries);
 }
 
-hipError_t launch_predecessors(const RayGeom &G, const float *v, const RayBox *boxes, int nstart,
-                               const RayEntry *entries, int nentries, bool exact, hipStream_t st)
+hipError_t launch_predecessors(const RayArgs &A, int nstart, bool exact, hipStream_t st)
 {
-    const long long N = (long long)G.n[0] * G.n[1] * G.n[2];
+    const long long N = (long long)A.G.n[0] * A.G.n[1] * A.G.n[2];
     if (N <= 0 || nstart <= 0) return hipSuccess;
     const long long nblocks = (N + RAY_BLOCK - 1) / RAY_BLOCK;
     if (nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -112,10 +110,10 @@ hipError_t launch_predecessors(const RayGeom &G, const float *v, const RayBox *b
     while (sb < RAY_SB && sb < nstart) sb *= 2;
     const dim3 grid((unsigned)nblocks, (unsigned)((nstart + sb - 1) / sb));
     switch (sb) {
-    case 1: launch_pred_sb<1>(grid, G, v, boxes, nstart, entries, nentries, exact, st); break;
-    case 2: launch_pred_sb<2>(grid, G, v, boxes, nstart, entries, nentries, exact, st); break;
-    case 4: launch_pred_sb<4>(grid, G, v, boxes, nstart, entries, nentries, exact, st); break;
-    default: launch_pred_sb<RAY_SB>(grid, G, v, boxes, nstart, entries, nentries, exact, st); break;
+    case 1: launch_pred_sb<1>(grid, A, nstart, exact, st); break;
+    case 2: launch_pred_sb<2>(grid, A, nstart, exact, st); break;
+    case 4: launch_pred_sb<4>(grid, A, nstart, exact, st); break;
+    default: launch_pred_sb<RAY_SB>(grid, A, nstart, exact, st); break;
     }
     return hipGetLastError();
 }
@@ -153,103 +151,13 @@ __device__ bool hop_length(const RayGeom &G, const float *__restrict__ v, const 
     return false;
 }
 
-// One lane per ray r = s * nrecv + q.  FILL = false: count[r] (cells of the path; 0 unless OK / SEED),
-// status[r], t_recv[r].  FILL = true: the same walk again, storing the path backwards into
-// [offsets[r], offsets[r + 1]) so that it reads source -> receiver.
-template <bool EXACT, bool FILL>
-__global__ void __launch_bounds__(RAY_BLOCK)
-trace_rays_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes, int nstart,
-                  const int *__restrict__ recv, int nrecv, const RayEntry *__restrict__ entries, int nentries,
-                  int *__restrict__ count, int *__restrict__ status, float *__restrict__ t_recv,
-                  const long long *__restrict__ offsets, int *__restrict__ cells, float *__restrict__ hop_d)
-{
-    const long long r = (long long)blockIdx.x * RAY_BLOCK + threadIdx.x;
-    if (r >= (long long)nstart * nrecv) return;
-    const int s = (int)(r / nrecv);
-    const int q = recv[r - (long long)s * nrecv];
-    const RayBox B = boxes[s];
-    const int N = G.n[0] * G.n[1] * G.n[2];
-    long long lo = 0, pos = 0;
-    if (FILL) {
-        lo = offsets[r];
-        pos = offsets[r + 1];
-        if (pos <= lo) return;
-        pos--;
-        cells[pos] = q;
-        hop_d[pos] = 0.0f;
-    }
-    float tc = B.T[q];
-    int st, n = 0;
-    if (ray_unreached(tc)) {
-        st = TTSWEEP_RAY_UNREACHED;
-    } else {
-        int c = q;
-        n = 1;
-        for (;;) {
-            const int p = B.pred[c];
-            if (p == TTSWEEP_PRED_SOURCE) { st = c == B.sflat ? TTSWEEP_RAY_OK : TTSWEEP_RAY_INVALID; break; }
-            if (p == TTSWEEP_PRED_SEED) { st = TTSWEEP_RAY_SEED; break; }
-            if (p < 0 || p >= N) { st = TTSWEEP_RAY_INVALID; break; }
-            const float tp = B.T[p];
-            // strictly decreasing travel times: a walk visits a cell at most once and ends
-            if (!(tp < tc)) { st = TTSWEEP_RAY_INVALID; break; }
-            float d = 0.0f;
-            if (!hop_length<EXACT>(G, v, entries, nentries, c, p, B.sflat, tc, tp, &d)) {
-                st = TTSWEEP_RAY_INVALID;
-                break;
-            }
-            n++;
-            if (FILL) {
-                if (pos <= lo) break;       // (the count pass saw this box: it cannot happen)
-                pos--;
-                cells[pos] = p;
-                hop_d[pos] = d;
-            }
-            c = p;
-            tc = tp;
-        }
-    }
-    if (!FILL) {
-        count[r] = (st == TTSWEEP_RAY_OK || st == TTSWEEP_RAY_SEED) ? n : 0;
-        status[r] = st;
-        t_recv[r] = B.T[q];
-    }
-}
-
-hipError_t launch_trace_rays(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
-                             int nrecv, const RayEntry *entries, int nentries, bool exact, int *count, int *status,
-                             float *t_recv, const long long *offsets, int *cells, float *hop_d, bool fill,
-                             hipStream_t st)
-{
-    const long long nrays = (long long)nstart * nrecv;
-    if (nrays <= 0) return hipSuccess;
-    const long long nblocks = (nrays + RAY_BLOCK - 1) / RAY_BLOCK;
-    if (nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    auto kernel = fill ? (exact ? trace_rays_kernel<true, true> : trace_rays_kernel<false, true>)
-                       : (exact ? trace_rays_kernel<true, false> : trace_rays_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, nstart, recv, nrecv,
-                       entries, nentries, count, status, t_recv, offsets, cells, hop_d);
-    return hipGetLastError();
-}
-
-
-// ---- the Frechet operators of the rays: G m and G^T w without storing a path ----
-// G is rays_to_frechet(trace_rays(...)): every hop p -> c of length d of an OK or SEED ray adds d / 2 at
-// (ray, p) and at (ray, c).  Both kernels walk one lane per ray r = s * nrecv + q like trace_rays_kernel (the
-// same checks per hop, the same statuses, the same hop_length<EXACT> choice of d) and read or scatter along
-// the walk instead of storing it.  UNREACHED and INVALID rays contribute nothing.
-// The ray_pairs_* kernels are the same bodies over a list of (box, receiver) records instead of the cross product,
-// and ray_pairs_geometry_kernel reads the geometry of each ray off the same walk (include/ttsweep.h, "rays: pair
-// lists").
-
-// The walk of trace_rays_kernel from receiver q of box B: hop(c, p, d) for every hop p -> c, in walk order
-// (receiver -> source).  Returns the ray's status; *end is the cell the walk ended at.
+// The walk from receiver q of box B along pred back to the start, checking every hop: hop(c, p, d) for every hop
+// p -> c of length d, in walk order (receiver -> source).  Returns the ray's status; *end is the cell the walk
+// ended at.
 template <bool EXACT, class Hop>
-__device__ __forceinline__ int ray_walk(const RayGeom &G, const float *__restrict__ v, const RayBox &B,
-                                        const RayEntry *__restrict__ entries, int nentries, int q, int *end,
-                                        Hop hop)
+__device__ __forceinline__ int ray_walk(const RayArgs &A, const RayBox &B, int q, int *end, Hop hop)
 {
-    const int N = G.n[0] * G.n[1] * G.n[2];
+    const int N = A.G.n[0] * A.G.n[1] * A.G.n[2];
     float tc = B.T[q];
     int c = q;
     *end = q;
@@ -261,61 +169,93 @@ __device__ __forceinline__ int ray_walk(const RayGeom &G, const float *__restric
         if (p == TTSWEEP_PRED_SEED) return TTSWEEP_RAY_SEED;
         if (p < 0 || p >= N) return TTSWEEP_RAY_INVALID;
         const float tp = B.T[p];
+        // strictly decreasing travel times: a walk visits a cell at most once and ends
         if (!(tp < tc)) return TTSWEEP_RAY_INVALID;
         float d = 0.0f;
-        if (!hop_length<EXACT>(G, v, entries, nentries, c, p, B.sflat, tc, tp, &d)) return TTSWEEP_RAY_INVALID;
+        if (!hop_length<EXACT>(A.G, A.v, A.entries, A.nentries, c, p, B.sflat, tc, tp, &d))
+            return TTSWEEP_RAY_INVALID;
         hop(c, p, d);
         c = p;
         tc = tp;
     }
 }
 
-// y[r] = (G m)[r]: y = y + (0.5 * (double)d) * (m[c] + m[p]) per hop p -> c in walk order from y = 0.0;
-// 0 for UNREACHED and INVALID rays.  One store per ray.  where(r, s, q): box and flat receiver of ray r (the
-// cross product r = s * nrecv + q of the dense call, or the record of a pair list).
-template <bool EXACT, class Where>
-__device__ __forceinline__ void ray_forward_body(const RayGeom &G, const float *__restrict__ v,
-                                                 const RayBox *__restrict__ boxes,
-                                                 const RayEntry *__restrict__ entries, int nentries, int r,
-                                                 Where where, const double *__restrict__ m,
-                                                 double *__restrict__ y, int *__restrict__ status)
+// box s and flat receiver q of ray r of the list: r = s * nrecv + q' with q = recv[q'] in a cross product, the
+// record of a pair list in one 8-byte load.  I: the type of a ray index (int but for the trace)
+template <bool PAIRS, class I>
+__device__ __forceinline__ void ray_of(const RayList &L, I r, int &s, int &q)
 {
-    int s, q;
-    where(r, s, q);
-    const RayBox B = boxes[s];
+    if (PAIRS) {
+        const RayPair pr = L.pairs[r];
+        s = pr.box;
+        q = pr.recv;
+    } else {
+        s = (int)(r / L.nrecv);
+        q = L.recv[r - (I)s * L.nrecv];
+    }
+}
+
+// One lane per ray of a cross product.  FILL = false: count[r] (cells of the path; 0 unless OK / SEED), status[r],
+// t_recv[r].  FILL = true: the same walk again, storing the path backwards into [offsets[r], offsets[r + 1]) so
+// that it reads source -> receiver.
+template <bool EXACT, bool FILL>
+__global__ void __launch_bounds__(RAY_BLOCK)
+trace_rays_kernel(RayArgs A, RayList L, int *__restrict__ count, int *__restrict__ status,
+                  float *__restrict__ t_recv, const long long *__restrict__ offsets, int *__restrict__ cells,
+                  float *__restrict__ hop_d)
+{
+    const long long r = (long long)blockIdx.x * RAY_BLOCK + threadIdx.x;
+    if (r >= L.n) return;
+    int s, q, end;
+    ray_of<false>(L, r, s, q);
+    const RayBox B = A.boxes[s];
+    if (FILL) {
+        const long long lo = offsets[r];
+        long long pos = offsets[r + 1];
+        if (pos <= lo) return;
+        pos--;
+        cells[pos] = q;
+        hop_d[pos] = 0.0f;
+        ray_walk<EXACT>(A, B, q, &end, [&](int, int p, float d) {
+            if (pos <= lo) return;          // (the count pass saw this box: it cannot happen)
+            pos--;
+            cells[pos] = p;
+            hop_d[pos] = d;
+        });
+    } else {
+        int n = 1;
+        const int st = ray_walk<EXACT>(A, B, q, &end, [&](int, int, float) { n++; });
+        count[r] = (st == TTSWEEP_RAY_OK || st == TTSWEEP_RAY_SEED) ? n : 0;
+        status[r] = st;
+        t_recv[r] = B.T[q];
+    }
+}
+
+// ---- the Frechet operators of the rays: G m and G^T w without storing a path ----
+// G is rays_to_frechet(trace_rays(...)): every hop p -> c of length d of an OK or SEED ray adds d / 2 at
+// (ray, p) and at (ray, c).  Both kernels walk one lane per ray like trace_rays_kernel (the same ray_walk, so the
+// same checks per hop, the same statuses, the same hop_length<EXACT> choice of d) and read or scatter along the walk
+// instead of storing it.  UNREACHED and INVALID rays contribute nothing.  PAIRS: the rays are the records of a pair
+// list instead of the cross product (ray_of), and ray_geometry_kernel reads the geometry of each ray off the same
+// walk (include/ttsweep.h, "rays: pair lists").
+
+// y[r] = (G m)[r]: y = y + (0.5 * (double)d) * (m[c] + m[p]) per hop p -> c in walk order from y = 0.0;
+// 0 for UNREACHED and INVALID rays.  One store per ray.
+template <bool EXACT, bool PAIRS>
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_forward_kernel(RayArgs A, RayList L, const double *__restrict__ m, double *__restrict__ y,
+                   int *__restrict__ status)
+{
+    const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
+    if (r >= (int)L.n) return;
+    int s, q, end;
+    ray_of<PAIRS>(L, r, s, q);
+    const RayBox B = A.boxes[s];
     double acc = 0.0;
-    int end;
-    const int st = ray_walk<EXACT>(G, v, B, entries, nentries, q, &end,
+    const int st = ray_walk<EXACT>(A, B, q, &end,
                                    [&](int c, int p, float d) { acc = acc + (0.5 * (double)d) * (m[c] + m[p]); });
     y[r] = (st == TTSWEEP_RAY_OK || st == TTSWEEP_RAY_SEED) ? acc : 0.0;
     status[r] = st;
-}
-
-template <bool EXACT>
-__global__ void __launch_bounds__(RAY_BLOCK)
-ray_forward_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes, int nstart,
-                   const int *__restrict__ recv, int nrecv, const RayEntry *__restrict__ entries, int nentries,
-                   const double *__restrict__ m, double *__restrict__ y, int *__restrict__ status)
-{
-    const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
-    if (r >= nstart * nrecv) return;
-    ray_forward_body<EXACT>(G, v, boxes, entries, nentries, r,
-                            [&](int r, int &s, int &q) { s = r / nrecv; q = recv[r - s * nrecv]; }, m, y, status);
-}
-
-// the same for a pair list: one lane per pair, the record in one 8-byte load
-template <bool EXACT>
-__global__ void __launch_bounds__(RAY_BLOCK)
-ray_pairs_forward_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes,
-                         const RayPair *__restrict__ pairs, int npair, const RayEntry *__restrict__ entries,
-                         int nentries, const double *__restrict__ m, double *__restrict__ y,
-                         int *__restrict__ status)
-{
-    const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
-    if (r >= npair) return;
-    ray_forward_body<EXACT>(G, v, boxes, entries, nentries, r,
-                            [&](int r, int &s, int &q) { const RayPair pr = pairs[r]; s = pr.box; q = pr.recv; },
-                            m, y, status);
 }
 
 // The fixed-point term of one visit: llrint(ldexp(w * (0.5 * ((double)d_in + (double)d_out)), S))
@@ -331,23 +271,21 @@ __device__ __forceinline__ long long ray_term(double w, float d_in, float d_out,
 // s ends at its start cell: those terms and hits are summed across the wave first, one atomic per wave and box.
 // Every lane of a wave reaches the wave sum (no early return).  The wave sum is keyed on the end cell, not on the
 // box: the lanes of one wave may belong to any boxes (a pair list), each distinct start cell gets its own round.
-// where(r, s, q): box and flat receiver of ray r, as in ray_forward_body.
-template <bool EXACT, class Where>
-__device__ __forceinline__ void ray_adjoint_body(const RayGeom &G, const float *__restrict__ v,
-                                                 const RayBox *__restrict__ boxes,
-                                                 const RayEntry *__restrict__ entries, int nentries, int r,
-                                                 int nrays, Where where, const double *__restrict__ w, int S,
-                                                 unsigned long long *__restrict__ acc, int *__restrict__ hits)
+template <bool EXACT, bool PAIRS>
+__global__ void __launch_bounds__(RAY_BLOCK)
+ray_adjoint_kernel(RayArgs A, RayList L, const double *__restrict__ w, int S, unsigned long long *__restrict__ acc,
+                   int *__restrict__ hits)
 {
-    const bool lane = r < nrays;
+    const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
+    const bool lane = r < (int)L.n;
     const double wr = (lane && w) ? w[r] : 0.0;
     const bool weighted = wr != 0.0;
     int st = TTSWEEP_RAY_UNREACHED, end = -1;
     float dlast = 0.0f;
     if (lane && (weighted || hits)) {
         int s, q;
-        where(r, s, q);
-        const RayBox B = boxes[s];
+        ray_of<PAIRS>(L, r, s, q);
+        const RayBox B = A.boxes[s];
         auto visit = [&](long long sign) {
             float dout = 0.0f;      // the hop out of the cell in the path's direction: none at the receiver
             return [&, sign, dout](int c, int, float d) mutable {
@@ -360,10 +298,10 @@ __device__ __forceinline__ void ray_adjoint_body(const RayGeom &G, const float *
                 dlast = d;
             };
         };
-        st = ray_walk<EXACT>(G, v, B, entries, nentries, q, &end, visit(1));
+        st = ray_walk<EXACT>(A, B, q, &end, visit(1));
         if (st == TTSWEEP_RAY_INVALID) {
             int e2;
-            ray_walk<EXACT>(G, v, B, entries, nentries, q, &e2, visit(-1));
+            ray_walk<EXACT>(A, B, q, &e2, visit(-1));
         }
         if (st == TTSWEEP_RAY_SEED) {           // the last cell of a SEED ray: not shared, one atomic of its own
             if (weighted) {
@@ -398,48 +336,23 @@ __device__ __forceinline__ void ray_adjoint_body(const RayGeom &G, const float *
     }
 }
 
-template <bool EXACT>
-__global__ void __launch_bounds__(RAY_BLOCK)
-ray_adjoint_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes, int nstart,
-                   const int *__restrict__ recv, int nrecv, const RayEntry *__restrict__ entries, int nentries,
-                   const double *__restrict__ w, int S, unsigned long long *__restrict__ acc,
-                   int *__restrict__ hits)
-{
-    ray_adjoint_body<EXACT>(G, v, boxes, entries, nentries, blockIdx.x * RAY_BLOCK + threadIdx.x, nstart * nrecv,
-                            [&](int r, int &s, int &q) { s = r / nrecv; q = recv[r - s * nrecv]; }, w, S, acc,
-                            hits);
-}
-
-template <bool EXACT>
-__global__ void __launch_bounds__(RAY_BLOCK)
-ray_pairs_adjoint_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes,
-                         const RayPair *__restrict__ pairs, int npair, const RayEntry *__restrict__ entries,
-                         int nentries, const double *__restrict__ w, int S, unsigned long long *__restrict__ acc,
-                         int *__restrict__ hits)
-{
-    ray_adjoint_body<EXACT>(G, v, boxes, entries, nentries, blockIdx.x * RAY_BLOCK + threadIdx.x, npair,
-                            [&](int r, int &s, int &q) { const RayPair pr = pairs[r]; s = pr.box; q = pr.recv; },
-                            w, S, acc, hits);
-}
-
 // The geometry of the ray of every pair, from the same walk.  Everything is kept in registers while the walk runs
 // and stored once it has returned its status: an INVALID ray is only known to be one when its walk fails.  Of the
 // first and the last hop the cells and d are kept; their offsets are decoded and their times read after the walk.
-template <bool EXACT>
+template <bool EXACT, bool PAIRS>
 __global__ void __launch_bounds__(RAY_BLOCK)
-ray_pairs_geometry_kernel(RayGeom G, const float *__restrict__ v, const RayBox *__restrict__ boxes,
-                          const RayPair *__restrict__ pairs, int npair, const RayEntry *__restrict__ entries,
-                          int nentries, int *__restrict__ status, RayGeometryOut O)
+ray_geometry_kernel(RayArgs A, RayList L, int *__restrict__ status, RayGeometryOut O)
 {
     const int r = blockIdx.x * RAY_BLOCK + threadIdx.x;
-    if (r >= npair) return;
-    const RayPair pr = pairs[r];
-    const RayBox B = boxes[pr.box];
-    const int q = pr.recv, nz = G.n[2], nyz = G.n[1] * G.n[2];
+    if (r >= (int)L.n) return;
+    int s, q;
+    ray_of<PAIRS>(L, r, s, q);
+    const RayBox B = A.boxes[s];
+    const int nz = A.G.n[2], nyz = A.G.n[1] * A.G.n[2];
     int hops = 0, first_p = q, last_c = q, deep = q, deepz = q % nz, end;
     float d_first = 0.0f, d_last = 0.0f;
     double length = 0.0;
-    const int st = ray_walk<EXACT>(G, v, B, entries, nentries, q, &end, [&](int c, int p, float d) {
+    const int st = ray_walk<EXACT>(A, B, q, &end, [&](int c, int p, float d) {
         if (hops == 0) {
             first_p = p;
             d_first = d;
@@ -517,18 +430,57 @@ ray_fixed_to_double_kernel(long long *__restrict__ g, long long n, int S)
     reinterpret_cast<double *>(g)[x] = t;
 }
 
-hipError_t launch_ray_forward(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
-                              int nrecv, const RayEntry *entries, int nentries, bool exact, const double *m,
-                              double *y, int *status, hipStream_t st)
+// One lane per ray: the blocks of nrays rays, the kernel of the `exact` choice, the launch's error.  limit: the rays
+// the kernel's index type holds.
+template <class Kernel, class... Args>
+static hipError_t launch_per_ray(bool exact, Kernel exact_kernel, Kernel kernel, long long nrays, long long limit,
+                                 hipStream_t st, const Args &...args)
 {
-    const long long nrays = (long long)nstart * nrecv;
     if (nrays <= 0) return hipSuccess;
-    if (nrays > 0x7fffffffLL) return hipErrorInvalidValue;
-    const unsigned nblocks = (unsigned)((nrays + RAY_BLOCK - 1) / RAY_BLOCK);
-    auto kernel = exact ? ray_forward_kernel<true> : ray_forward_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, nstart, recv, nrecv, entries,
-                       nentries, m, y, status);
+    const long long nblocks = (nrays + RAY_BLOCK - 1) / RAY_BLOCK;
+    if (nrays > limit || nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(exact ? exact_kernel : kernel, dim3((unsigned)nblocks), dim3(RAY_BLOCK), 0, st, args...);
     return hipGetLastError();
+}
+
+constexpr long long RAY_INT32 = 0x7fffffffLL, RAY_INT64 = 0x7fffffffffffffffLL;
+
+hipError_t launch_trace_rays(const RayArgs &A, const RayList &L, bool exact, int *count, int *status, float *t_recv,
+                             const long long *offsets, int *cells, float *hop_d, bool fill, hipStream_t st)
+{
+    if (fill)
+        return launch_per_ray(exact, trace_rays_kernel<true, true>, trace_rays_kernel<false, true>, L.n, RAY_INT64,
+                              st, A, L, count, status, t_recv, offsets, cells, hop_d);
+    return launch_per_ray(exact, trace_rays_kernel<true, false>, trace_rays_kernel<false, false>, L.n, RAY_INT64, st,
+                          A, L, count, status, t_recv, offsets, cells, hop_d);
+}
+
+hipError_t launch_ray_forward(const RayArgs &A, const RayList &L, bool exact, const double *m, double *y, int *status,
+                              hipStream_t st)
+{
+    if (L.pairs)
+        return launch_per_ray(exact, ray_forward_kernel<true, true>, ray_forward_kernel<false, true>, L.n, RAY_INT32,
+                              st, A, L, m, y, status);
+    return launch_per_ray(exact, ray_forward_kernel<true, false>, ray_forward_kernel<false, false>, L.n, RAY_INT32,
+                          st, A, L, m, y, status);
+}
+
+hipError_t launch_ray_adjoint(const RayArgs &A, const RayList &L, bool exact, const double *w, int S, long long *acc,
+                              int *hits, hipStream_t st)
+{
+    unsigned long long *const sums = (unsigned long long *)acc;
+    if (L.pairs)
+        return launch_per_ray(exact, ray_adjoint_kernel<true, true>, ray_adjoint_kernel<false, true>, L.n, RAY_INT32,
+                              st, A, L, w, S, sums, hits);
+    return launch_per_ray(exact, ray_adjoint_kernel<true, false>, ray_adjoint_kernel<false, false>, L.n, RAY_INT32,
+                          st, A, L, w, S, sums, hits);
+}
+
+hipError_t launch_ray_pairs_geometry(const RayArgs &A, const RayList &L, bool exact, int *status,
+                                     const RayGeometryOut &out, hipStream_t st)
+{
+    return launch_per_ray(exact, ray_geometry_kernel<true, true>, ray_geometry_kernel<false, true>, L.n, RAY_INT32,
+                          st, A, L, status, out);
 }
 
 hipError_t launch_ray_weight_scan(const double *w, int n, int *out, hipStream_t st)
@@ -537,56 +489,6 @@ hipError_t launch_ray_weight_scan(const double *w, int n, int *out, hipStream_t 
     const int want = (n + RAY_BLOCK - 1) / RAY_BLOCK;
     const unsigned nblocks = (unsigned)(want < 1024 ? want : 1024);
     hipLaunchKernelGGL(ray_weight_scan_kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, w, n, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_ray_adjoint(const RayGeom &G, const float *v, const RayBox *boxes, int nstart, const int *recv,
-                              int nrecv, const RayEntry *entries, int nentries, bool exact, const double *w, int S,
-                              long long *acc, int *hits, hipStream_t st)
-{
-    const long long nrays = (long long)nstart * nrecv;
-    if (nrays <= 0) return hipSuccess;
-    if (nrays > 0x7fffffffLL) return hipErrorInvalidValue;
-    const unsigned nblocks = (unsigned)((nrays + RAY_BLOCK - 1) / RAY_BLOCK);
-    auto kernel = exact ? ray_adjoint_kernel<true> : ray_adjoint_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, nstart, recv, nrecv, entries,
-                       nentries, w, S, (unsigned long long *)acc, hits);
-    return hipGetLastError();
-}
-
-hipError_t launch_ray_pairs_forward(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
-                                    int npair, const RayEntry *entries, int nentries, bool exact, const double *m,
-                                    double *y, int *status, hipStream_t st)
-{
-    if (npair <= 0) return hipSuccess;
-    const unsigned nblocks = (unsigned)(((long long)npair + RAY_BLOCK - 1) / RAY_BLOCK);
-    auto kernel = exact ? ray_pairs_forward_kernel<true> : ray_pairs_forward_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, pairs, npair, entries, nentries,
-                       m, y, status);
-    return hipGetLastError();
-}
-
-hipError_t launch_ray_pairs_adjoint(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
-                                    int npair, const RayEntry *entries, int nentries, bool exact, const double *w,
-                                    int S, long long *acc, int *hits, hipStream_t st)
-{
-    if (npair <= 0) return hipSuccess;
-    const unsigned nblocks = (unsigned)(((long long)npair + RAY_BLOCK - 1) / RAY_BLOCK);
-    auto kernel = exact ? ray_pairs_adjoint_kernel<true> : ray_pairs_adjoint_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, pairs, npair, entries, nentries,
-                       w, S, (unsigned long long *)acc, hits);
-    return hipGetLastError();
-}
-
-hipError_t launch_ray_pairs_geometry(const RayGeom &G, const float *v, const RayBox *boxes, const RayPair *pairs,
-                                     int npair, const RayEntry *entries, int nentries, bool exact, int *status,
-                                     const RayGeometryOut &out, hipStream_t st)
-{
-    if (npair <= 0) return hipSuccess;
-    const unsigned nblocks = (unsigned)(((long long)npair + RAY_BLOCK - 1) / RAY_BLOCK);
-    auto kernel = exact ? ray_pairs_geometry_kernel<true> : ray_pairs_geometry_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(RAY_BLOCK), 0, st, G, v, boxes, pairs, npair, entries, nentries,
-                       status, out);
     return hipGetLastError();
 }
 

@@ -195,6 +195,16 @@ class TravelTimeSolver:
                                                    self._box_pointers(pred, n)), "ttsweep_predecessors_device")
         return pred
 
+    def _require_pred(self, starts, tt, pred):
+        """pred of the boxes tt: the caller's, checked, or the result of predecessors() when None."""
+        import torch
+        if pred is None:
+            return self.predecessors(starts, tt)
+        _require(isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_contiguous()
+                 and tuple(pred.shape) == tuple(tt.shape) and pred.device == tt.device,
+                 "pred: contiguous int32 tensor of the boxes' shape on their device")
+        return pred
+
     def trace_rays(self, starts, tt, receivers, pred=None) -> "Rays":
         """ttsweep_trace_rays_device: the ray from every start of tt to every receiver ((nrecv, 3) cells),
         ray r = s * nrecv + q.  pred: the result of predecessors() for these boxes (computed when None).
@@ -203,11 +213,7 @@ class TravelTimeSolver:
         arr = self._starts_array(starts)
         n = len(arr)
         self._require_device_tensor(tt, (n,) + self.shape, "travel-time boxes")
-        if pred is None:
-            pred = self.predecessors(starts, tt)
-        _require(isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_contiguous()
-                 and tuple(pred.shape) == tuple(tt.shape) and pred.device == tt.device,
-                 "pred: contiguous int32 tensor of the boxes' shape on their device")
+        pred = self._require_pred(starts, tt, pred)
         recv = self._starts_array(receivers)
         nrays = n * len(recv)
         offsets = torch.zeros(nrays + 1, dtype=torch.int64)
@@ -252,11 +258,7 @@ class TravelTimeSolver:
         arr = self._starts_array(starts)
         n = len(arr)
         self._require_device_tensor(tt, (n,) + self.shape, "travel-time boxes")
-        if pred is None:
-            pred = self.predecessors(starts, tt)
-        _require(isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_contiguous()
-                 and tuple(pred.shape) == tuple(tt.shape) and pred.device == tt.device,
-                 "pred: contiguous int32 tensor of the boxes' shape on their device")
+        pred = self._require_pred(starts, tt, pred)
         box, recv = self._pair_arrays(pair_box, pair_recv)
         npair = len(recv)
         dev = tt.device
@@ -737,7 +739,60 @@ class ConfidenceRegions:
         return (_host(self.count) > 0) & np.any((lo == 0) | (hi == top), axis=-1)
 
 
-class FrechetOperator:
+class _CellOperator:
+    """What FrechetOperator and FresnelOperator share: an operator [nrows, nx*ny*nz] whose adjoint is one call of the
+    C ABI that sums in int64 fixed point.  A subclass sets shape, grid, device and last_scale, and supplies
+    _adjoint_call(w, g, hits, scale) (the C call on device pointers or None; returns (rc, the call's name)) and, where
+    its rows carry coefficients, _row_weights(w)."""
+
+    def _cells(self, t, what):
+        import torch
+        _require(isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == self.device,
+                 f"{what}: float64 tensor on {self.device}")
+        _require(t.numel() == self.shape[1] and tuple(t.shape) in ((self.shape[1],), self.grid),
+                 f"{what}: shape {tuple(t.shape)}, want {self.grid} or ({self.shape[1]},)")
+        return t.contiguous()
+
+    def _row_weights(self, w):
+        return w
+
+    def _adjoint(self, w, hits):
+        import torch
+        scale = C.c_int(0)
+        g = None
+        if w is not None:
+            _require(isinstance(w, torch.Tensor) and w.dtype == torch.float64 and w.device == self.device
+                     and tuple(w.shape) == (self.shape[0],), f"w: float64 [{self.shape[0]}] on {self.device}")
+            w = self._row_weights(w).contiguous()
+            g = torch.empty(self.grid, dtype=torch.float64, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _check(*self._adjoint_call(ptr(w), ptr(g), ptr(hits), C.byref(scale)))
+        if w is not None:
+            self.last_scale = scale.value
+        return g
+
+    def rmatvec(self, w):
+        """A^T w (FresnelOperator: F^T (coef * w)): w float64 [nrows] on the device; float64 [nx,ny,nz], deterministic
+        (int64 fixed point)."""
+        return self._adjoint(w, None)
+
+    def rmatvec_hits(self, w):
+        """(rmatvec(w), hits) of one walk of the rays, or one pass over the pairs."""
+        import torch
+        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
+        return self._adjoint(w, hits), hits
+
+    def hits(self):
+        """int32 [nx,ny,nz]: the number of OK or SEED rays whose path holds each cell (FresnelOperator: of pairs whose
+        volume holds it)."""
+        import torch
+        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
+        self._adjoint(None, hits)
+        return hits
+
+
+class FrechetOperator(_CellOperator):
     """G [nrays, nx*ny*nz] of TravelTimeSolver.trace_rays + rays_to_frechet, applied by walking the rays on the
     device instead of storing them (TravelTimeSolver.frechet_operator).  Holds the solver, the boxes, pred and
     the start and receiver lists as C arrays (built once); the boxes and pred must not change while it is used.
@@ -752,11 +807,7 @@ class FrechetOperator:
         self._starts = solver._starts_array(starts)
         n = len(self._starts)
         solver._require_device_tensor(tt, (n,) + solver.shape, "travel-time boxes")
-        if pred is None:
-            pred = solver.predecessors(starts, tt)
-        _require(isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_contiguous()
-                 and tuple(pred.shape) == tuple(tt.shape) and pred.device == tt.device,
-                 "pred: contiguous int32 tensor of the boxes' shape on their device")
+        pred = solver._require_pred(starts, tt, pred)
         self.tt, self.pred = tt, pred
         self._tptr, self._pptr = solver._box_pointers(tt, n), solver._box_pointers(pred, n)
         self.grid = solver.shape
@@ -788,14 +839,6 @@ class FrechetOperator:
             box = torch.from_numpy(np.frombuffer(self._pair_box, dtype=np.int32)[:nrays].astype(np.int64))
             self.t_recv = tt.reshape(n, -1)[box.to(tt.device), flat].cpu()
 
-    def _cells(self, t, what):
-        import torch
-        _require(isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == self.device,
-                 f"{what}: float64 tensor on {self.device}")
-        _require(t.numel() == self.shape[1] and tuple(t.shape) in ((self.shape[1],), self.grid),
-                 f"{what}: shape {tuple(t.shape)}, want {self.grid} or ({self.shape[1]},)")
-        return t.contiguous()
-
     def _forward(self, m, status=None):
         import torch
         y = torch.empty(self.shape[0], dtype=torch.float64, device=self.device)
@@ -808,39 +851,8 @@ class FrechetOperator:
         """G m: m float64 [nx,ny,nz] or [ncells] on the device; float64 [nrays]."""
         return self._forward(self._cells(m, "m"))
 
-    def _adjoint(self, w, hits):
-        import torch
-        scale = C.c_int(0)
-        g = None
-        if w is not None:
-            _require(isinstance(w, torch.Tensor) and w.dtype == torch.float64 and w.device == self.device
-                     and tuple(w.shape) == (self.shape[0],), f"w: float64 [{self.shape[0]}] on {self.device}")
-            w = w.contiguous()
-            g = torch.empty(self.grid, dtype=torch.float64, device=self.device)
-        torch.cuda.current_stream(self.device).synchronize()
-        _check(self._calls[2](self._sol._ctx, *self._rays, None if w is None else w.data_ptr(),
-                              None if g is None else g.data_ptr(), None if hits is None else hits.data_ptr(),
-                              C.byref(scale)), self._calls[3])
-        if w is not None:
-            self.last_scale = scale.value
-        return g
-
-    def rmatvec(self, w):
-        """G^T w: w float64 [nrays] on the device; float64 [nx,ny,nz], deterministic (int64 fixed point)."""
-        return self._adjoint(w, None)
-
-    def rmatvec_hits(self, w):
-        """(G^T w, hits) of one walk."""
-        import torch
-        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
-        return self._adjoint(w, hits), hits
-
-    def hits(self):
-        """int32 [nx,ny,nz]: the number of OK or SEED rays whose path holds each cell."""
-        import torch
-        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
-        self._adjoint(None, hits)
-        return hits
+    def _adjoint_call(self, w, g, hits, scale):
+        return self._calls[2](self._sol._ctx, *self._rays, w, g, hits, scale), self._calls[3]
 
 
 @dataclass
@@ -872,7 +884,7 @@ class FresnelVolumes:
         return lo, hi
 
 
-class FresnelOperator:
+class FresnelOperator(_CellOperator):
     """F [npair, nx*ny*nz] with F[r, x] = coef[r] * phi_r(x), applied by streaming the two boxes of every pair on the
     device (TravelTimeSolver.fresnel_operator); lsqr takes it as it is.  The boxes must not change while it is used.
       shape      (npair, ncells)
@@ -902,14 +914,6 @@ class FresnelOperator:
         self.last_scale = 0
         self.last_forward_scale = 0
 
-    def _cells(self, t, what):
-        import torch
-        _require(isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == self.device,
-                 f"{what}: float64 tensor on {self.device}")
-        _require(t.numel() == self.shape[1] and tuple(t.shape) in ((self.shape[1],), self.grid),
-                 f"{what}: shape {tuple(t.shape)}, want {self.grid} or ({self.shape[1]},)")
-        return t.contiguous()
-
     def forward_raw(self, m):
         """y = F m without the row coefficients: ttsweep_fresnel_forward_device as it is."""
         import torch
@@ -926,39 +930,12 @@ class FresnelOperator:
         """coef * (F m): m float64 [nx,ny,nz] or [ncells] on the device; float64 [npair]."""
         return self.coef * self.forward_raw(m)
 
-    def _adjoint(self, w, hits):
-        import torch
-        scale = C.c_int(0)
-        g = None
-        if w is not None:
-            _require(isinstance(w, torch.Tensor) and w.dtype == torch.float64 and w.device == self.device
-                     and tuple(w.shape) == (self.shape[0],), f"w: float64 [{self.shape[0]}] on {self.device}")
-            w = (self.coef * w).contiguous()
-            g = torch.empty(self.grid, dtype=torch.float64, device=self.device)
-        torch.cuda.current_stream(self.device).synchronize()
-        _check(self._sol._L.ttsweep_fresnel_adjoint_device(
-            *self._args[:10], None if w is None else w.data_ptr(), None if g is None else g.data_ptr(),
-            None if hits is None else hits.data_ptr(), None, C.byref(scale)), "ttsweep_fresnel_adjoint_device")
-        if w is not None:
-            self.last_scale = scale.value
-        return g
+    def _row_weights(self, w):
+        return self.coef * w
 
-    def rmatvec(self, w):
-        """F^T (coef * w): w float64 [npair] on the device; float64 [nx,ny,nz], deterministic (int64 fixed point)."""
-        return self._adjoint(w, None)
-
-    def rmatvec_hits(self, w):
-        """(F^T (coef * w), hits) of one pass."""
-        import torch
-        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
-        return self._adjoint(w, hits), hits
-
-    def hits(self):
-        """int32 [nx,ny,nz]: the number of pairs whose volume holds each cell."""
-        import torch
-        hits = torch.empty(self.grid, dtype=torch.int32, device=self.device)
-        self._adjoint(None, hits)
-        return hits
+    def _adjoint_call(self, w, g, hits, scale):
+        return (self._sol._L.ttsweep_fresnel_adjoint_device(*self._args[:10], w, g, hits, None, scale),
+                "ttsweep_fresnel_adjoint_device")
 
 
 def lsqr(A, b, damp=0.0, atol=1e-8, btol=1e-8, iter_lim=None):
