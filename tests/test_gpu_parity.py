@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, assert_bit_equal
+from conftest import GOLDEN, Golden, assert_bit_equal
 from strip_cases import SCHEDULES
 
 pytestmark = pytest.mark.gpu
@@ -1176,6 +1176,94 @@ def test_context_reuse_and_edge_arguments(P, golden24, oracle):
         P.TravelTimeSolver((0, 4, 4), fs)
     with pytest.raises(P.TTSweepError):
         P.TravelTimeSolver(v1.shape, fs, device=99)
+
+
+@pytest.mark.parametrize("sname", ["six", "nonsym"])
+def test_one_context_grows_every_pool_switches_kernels_and_goes(P, sname):
+    """One context whose pools all have to grow or be made again: 1 start, then 3; every kernel variant in turn (a new
+    layout each time, the velocity set again) with 2 starts; host boxes in batches of 1, then all at once (the
+    staging stack grows); rays to 1 receiver, then to 50 (the ray buffer grows); then it is destroyed.  Every call
+    gives bit for bit what a context made for that call alone gives, and the process goes on with a new context.
+    (six: the TILE variant runs the column driver; nonsym: the hyperplane launches.)"""
+    import torch
+    g = Golden("g9")
+    v, offs = g.v, g.star(sname)
+    fs = P.inputs.make_fs(offs)
+    variants = []                               # the kernel variants that accept this star
+    with P.TravelTimeSolver(v.shape, fs) as probe:
+        for k in (P.KERNEL_CELL, P.KERNEL_STRIP, P.KERNEL_TILE):
+            try:
+                probe.set_option(P.OPT_KERNEL, k)
+                variants.append(k)
+            except P.TTSweepError:
+                pass
+    assert len(variants) == 3 and tile_supports(offs)      # (a small star: none is left out)
+    dev = torch.device("cuda:0")
+    one, two = np.array([[4, 3, 2]], np.int32), np.array([[1, 5, 3], [7, 1, 0]], np.int32)
+    three = np.array([[4, 3, 2], [0, 0, 0], [8, 6, 4]], np.int32)
+    key = f"{sname}_mid"
+    solved = torch.from_numpy(g.z[f"tt_{key}"][None].copy()).to(dev)
+    cells = np.argwhere(np.ones(v.shape, bool)).astype(np.int32)
+
+    def on_device(starts):
+        def call(sol):
+            tt = torch.empty((len(starts),) + v.shape, dtype=torch.float32, device=dev)
+            rc = sol.solve_device(starts, tt, init=True)
+            return [np.int32(rc), np.array(sol.changed(len(starts)), np.int32), tt.cpu().numpy()]
+        return call
+
+    def on_host(starts):
+        def call(sol):
+            tts = []
+            for st in starts:
+                tt = np.full(v.shape, np.inf, dtype=np.float32)
+                tt[tuple(st)] = 0
+                tts.append(tt)
+            rc = sol.solve(starts, tts)
+            return [np.int32(rc), np.array(sol.changed(len(starts)), np.int32)] + tts
+        return call
+
+    def rays(recv):
+        def call(sol):
+            r = sol.trace_rays(g.z[f"start_{key}"][None], solved, recv)
+            assert np.all(r.status.numpy() != P.RAY_INVALID)
+            return [r.offsets.numpy(), r.status.numpy(), r.t_recv.numpy(), r.cells.cpu().numpy(), r.hop_d.cpu().numpy()]
+        return call
+
+    # (what, options set before the call, the call)
+    steps = [("1 start", {}, on_device(one)), ("3 starts", {}, on_device(three))]
+    steps += [(f"2 starts, kernel {k}", {P.OPT_KERNEL: k}, on_device(two)) for k in variants]
+    steps += [("host boxes one by one", {P.OPT_MAX_BATCH: 1}, on_host(three)),
+              ("host boxes at once", {P.OPT_MAX_BATCH: 0}, on_host(three)),
+              ("1 receiver", {}, rays(cells[100:101])), ("50 receivers", {}, rays(cells[::6][:50]))]
+
+    reused = []
+    with P.TravelTimeSolver(v.shape, fs) as sol:
+        sol.set_velocity(v)
+        for what, options, call in steps:
+            for k, value in options.items():
+                sol.set_option(k, value)
+            if P.OPT_KERNEL in options:
+                sol.set_velocity(v)             # (a new layout drops the padded copy)
+            reused.append(call(sol))
+            if P.OPT_KERNEL in options:
+                assert sol.stats()["kernel_variant"] == options[P.OPT_KERNEL], what
+    so_far = {}
+    for (what, options, call), got in zip(steps, reused):
+        so_far.update(options)
+        with P.TravelTimeSolver(v.shape, fs) as sol:
+            for k, value in so_far.items():
+                sol.set_option(k, value)
+            sol.set_velocity(v)
+            want = call(sol)
+        assert len(got) == len(want), what
+        for a, b in zip(got, want):
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), what
+    rc_of = {what: got[0] for (what, _, _), got in zip(steps, reused)}
+    assert rc_of["1 start"] == 1 and rc_of["host boxes one by one"] == 1 and len(reused[-1][1]) == 50
+    (tt,), rc, _ = gpu_converge(P, v, fs, [g.z[f"start_{key}"]])
+    assert rc == 1
+    assert_bit_equal(tt, g.z[f"tt_{key}"], key)
 
 
 def test_duplicate_and_zero_offsets_in_the_star(P, oracle):

@@ -18,6 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "owned_buffer.h"
 #include "pullstar.h"
 #include "scratch_layout.h"
 #include "ttsweep_dev.h"
@@ -28,21 +29,25 @@ namespace ttsweep {
 // error text of the calling thread (ttsweep_last_error); returns -1
 int set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 
+// Device memory owned by an OwnedBuffer (owned_buffer.h): released with its owner, or by alloc() / reserve() /
+// reset(), which hand the runtime's error code on.
+struct DevMem {
+    static int alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static int release(void *p) { return hipFree(p); }
+};
+template <class T> using DevBuf = OwnedBuffer<T, DevMem>;
+
 // The device scratch of one call: add() declares the arrays (scratch_layout.h), alloc() allocates them as one block
 // of its own, freed with the object.  (The ray calls place the same layout into ctx->d_rays instead.)
 class Scratch : public ScratchLayout {
-    char *p = nullptr;
+    DevBuf<char> block;
 
 public:
-    ~Scratch()
-    {
-        if (p) (void)hipFree(p);
-    }
     hipError_t alloc()
     {
-        const hipError_t err = hipMalloc((void **)&p, size());
-        if (err == hipSuccess) place(p);
-        return err;
+        const int err = block.alloc(size());
+        if (err == 0) place(block);
+        return static_cast<hipError_t>(err);
     }
 };
 
