@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, assert_bit_equal
+from tile_cases import tile_supports
 
 pytestmark = pytest.mark.gpu
 
@@ -75,13 +76,6 @@ def exact_instance(v, fs):
     huge = 2.0 ** 126 / float(pos.max())
     vv = v.astype(np.float64)
     return bool(np.any((vv > 0) & (vv < float(F32(tiny)))) or np.any(vv >= float(F32(huge))))
-
-
-def tile_supports(offs):
-    """Mirror of the library's rule for the TILE kernel (small stars only)."""
-    pull = {tuple(o) for o in offs[:-1]} | {tuple(-o) for o in offs[:-1]}
-    pull.discard((0, 0, 0))
-    return 0 < len(pull) <= 26 and all(abs(a) <= 2 and abs(b) <= 2 and abs(c) <= 4 for a, b, c in pull)
 
 
 def boxes_for(shape, starts):

@@ -13,6 +13,7 @@ import pytest
 
 from conftest import GOLDEN, Golden, assert_bit_equal
 from strip_cases import SCHEDULES
+from tile_cases import tile_supports
 
 pytestmark = pytest.mark.gpu
 
@@ -49,13 +50,6 @@ def gpu_converge(P, v, fs, starts, starstart=0, starstop=None, tts=None, kernel=
 
 KERNELS = [pytest.param(1, id="cell"), pytest.param(21, id="strip1"), pytest.param(22, id="strip2"),
            pytest.param(23, id="strip1-passes"), pytest.param(24, id="strip2-passes")]
-
-
-def tile_supports(offs):
-    """Mirror of the library's rule for the TILE kernel (small stars only)."""
-    pull = {tuple(o) for o in offs[:-1]} | {tuple(-o) for o in offs[:-1]}
-    pull.discard((0, 0, 0))
-    return 0 < len(pull) <= 26 and all(abs(a) <= 2 and abs(b) <= 2 and abs(c) <= 4 for a, b, c in pull)
 
 
 @pytest.mark.parametrize("kernel", KERNELS + [pytest.param(3, id="tile")])
