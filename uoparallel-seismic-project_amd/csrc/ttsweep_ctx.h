@@ -4,7 +4,9 @@
 //   ttsweep_plan.cpp    what is decided once per context or solve: padded layouts, which kernel
 //                       relaxes a star, the STRIP kernel's items and unit order, capacity
 //   ttsweep_driver.cpp  the driver loop of serial_new/sweep-tt-multistart.c:151-170 (without the
-//                       break, :168-169): passes enqueued one ahead of the convergence test
+//                       break, :168-169) as phases: set up, one launch, passes enqueued one ahead
+//                       of the convergence test, finish; its rules over plain numbers are in
+//                       driver_rules.h (no HIP header)
 // There is no CPU relaxation in any of them: every solve runs HIP kernels or fails.
 #pragma once
 
