@@ -1,6 +1,7 @@
 """Shared cases of the STRIP kernel's schedule tests (test_gpu_parity.py, test_gpu_strip_schedules.py): the option
 sets, the two grids whose units have neighbours on every axis, a host-side mirror of the library's layout rule, and
-the helpers that make fresh boxes and set options.  Plain module: no test lives here."""
+the helpers that make fresh boxes, set options and damage converged boxes (shared with test_gpu_strip_stars.py).
+Plain module: no test lives here."""
 import os
 import re
 from concurrent.futures import ThreadPoolExecutor
@@ -205,6 +206,22 @@ def second_starts():
 
 def velocity(shape):
     return np.random.default_rng(SEED).uniform(0.1, 0.5, size=shape).astype(np.float32)
+
+
+INF = np.float32(np.inf)
+
+
+def damage_to_infinity(grid, box, start):
+    """INFINITY in a 5x5x5 block across the lane-tile boundary, in one across a strip boundary, in the whole last
+    plane and in the ragged lane tile; the start keeps its 0."""
+    L = grid.layout
+    tile, strip = (L.btiles - 1) * L.TB, 2 * L.K
+    box[L.block(slice(30, 35), slice(tile - 2, tile + 3), slice(20, 25))] = INF
+    box[L.block(slice(10, 15), slice(10, 15), slice(strip - 2, strip + 3))] = INF
+    box[L.block(slice(L.planes - 1, L.planes), slice(None), slice(None))] = INF
+    box[L.block(slice(None), slice(tile, L.nb), slice(None))] = INF
+    box[tuple(start)] = 0
+    return box
 
 
 def oracle_boxes(oracle, v, offs, starts, tts=None):

@@ -11,12 +11,11 @@ import pytest
 
 import strip_cases as S
 from conftest import assert_bit_equal
-from strip_cases import SCHEDULES, schedule_id
+from strip_cases import SCHEDULES, damage_to_infinity, schedule_id
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(180)]
 
 STRIP = 2
-INF = np.float32(np.inf)
 
 
 @pytest.fixture(scope="module")
@@ -153,19 +152,6 @@ def test_queues_starts_and_unit_size(P, main, queues, nstart, pair, one_launch):
 
 DRIVERS = [pytest.param(1, 1 << 20, id="one-launch-one-plane"), pytest.param(1, 0, id="one-launch-two-plane"),
            pytest.param(0, 1 << 20, id="passes-one-plane"), pytest.param(0, 0, id="passes-two-plane")]
-
-
-def damage_to_infinity(grid, box, start):
-    """INFINITY in a 5x5x5 block across the lane-tile boundary, in one across a strip boundary, in the whole last
-    plane and in the ragged lane tile; the start keeps its 0."""
-    L = grid.layout
-    tile, strip = (L.btiles - 1) * L.TB, 2 * L.K
-    box[L.block(slice(30, 35), slice(tile - 2, tile + 3), slice(20, 25))] = INF
-    box[L.block(slice(10, 15), slice(10, 15), slice(strip - 2, strip + 3))] = INF
-    box[L.block(slice(L.planes - 1, L.planes), slice(None), slice(None))] = INF
-    box[L.block(slice(None), slice(tile, L.nb), slice(None))] = INF
-    box[tuple(start)] = 0
-    return box
 
 
 def far_cell(shape, start):
